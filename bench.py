@@ -16,6 +16,14 @@ SURVEY.md §8e).  Weak scaling: the swarm grows to round(1024 sqrt(G)) agents
 so that every GPU keeps C3's ~1.05 M pairs per step (the path is all-pairs,
 O(N^2)); --agents fixes N instead (e.g. --agents 4096 at G = 8 is C4).
 
+A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`); --dump-outputs DIR also writes the last timed
+step's new velocities to DIR/newv.npy (float64, all N rows; the swarm is
+seeded, so equal arguments give equal inputs).  --full adds what is measured
+beside the headline in runs of its own: the canonical hull rule, the closed
+loop, the C++ host, the k_pair roofline probe and the critical path, the
+C4 / C5 configurations and the CPU baseline.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -478,6 +486,13 @@ def main():
                     help="whose timed steps are `value`: the Python host (lqro.step_rows) or the C++ host "
                          "(lqro::ShardedSimulator, a child process per rank); the other is reported beside it")
     ap.add_argument("--no-host-cpp", action="store_true", help="skip the C++ host run (python host only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what is reported beside the headline: the canonical hull "
+                         "rule, the closed loop, the C++ host, the k_pair roofline probe, the C4 / C5 configurations "
+                         "and the CPU baseline (each with its --no-... switch); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the new velocities of the last timed step (what a caller of the timed path "
+                         "receives) to DIR/newv.npy, float64 (N, 3)")
     args = ap.parse_args()
 
     import torch
@@ -570,7 +585,12 @@ def main():
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     st = ctx.stats()
-    crit = critical_path(ctx) if flags & lqro.LQRO_FLAG_QHULL_ORDER else None
+    crit = critical_path(ctx) if args.full and flags & lqro.LQRO_FLAG_QHULL_ORDER else None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's newV, before anything below reuses d_newv (all
+        # rows: with more than one rank the step ends with their all-gather)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "newv.npy"), d_newv.cpu().numpy().astype(np.float64, copy=False))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -591,13 +611,17 @@ def main():
     # the closed loop runs before the probe creates a second context (whose
     # stream can share a hardware queue with this context's side stream)
     ctx.close()   # one context at a time: a second one's streams can share hardware queues
+    # a plain run stops at the headline: everything measured beside it, in
+    # runs of its own, is --full's (--host cpp's child is the headline itself)
     other = None
-    if args.hull_rule == "qhull":
+    if args.full and args.hull_rule == "qhull":
         other = canonical_rule_run(lqro, torch, dev, sh, gains, d_x, d_vg, d_newv, stream, args.steps, N, world, rank,
                                    args.rows)
-    closed = closed_loop(lqro, torch, dev, x, vg, gains, min(args.steps, 5), world, dist, rank, args.rows, flags)
+    closed = None
+    if args.full:
+        closed = closed_loop(lqro, torch, dev, x, vg, gains, min(args.steps, 5), world, dist, rank, args.rows, flags)
     host_cpp = None
-    if args.host == "cpp" or not args.no_host_cpp:
+    if args.host == "cpp" or (args.full and not args.no_host_cpp):
         if args.rows != "block" or args.hull_rule != "qhull":
             host_cpp = {"error": "the C++ host shards rows in blocks with the reference's hull rule"}
         else:
@@ -605,7 +629,7 @@ def main():
                                     args.warmup if args.host == "cpp" else 1, world, rank, local, dist)
     pk_ms = sweep_ms
     probe = "sweep (k_prio + k_pair launches + overlapped side hull), timed steps"
-    if not args.no_roofline_probe:
+    if args.full and not args.no_roofline_probe:
         os.environ["LQRO_HOT"] = "0"
         pctx = lqro.Context(lqro.config(N, HORIZON, N_POINTS, device=local, flags=0, **sh))   # k_pair only
         del os.environ["LQRO_HOT"]
@@ -629,6 +653,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": ms_step,
         "higher_is_better": True,
         "scaling": "weak" if world > 1 else "none",   # (weak: the swarm grows with the ranks; N = 1: no scaling)
@@ -685,9 +710,9 @@ def main():
                 out["host_python"] = {"value": value, "ms_per_step": ms_step}
                 out["value"], out["ms_per_step"] = host_cpp["value"], host_cpp["ms_per_step"]
                 out["config"]["host"] = "cpp"
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         out["configs"] = config_runs(lqro, torch, dev, local, world, rank, dist, 2, args.rows, flags)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(x, vg, gains, args.hull_rule)
         out["cpu_baseline"] = cb
         out["gpu_over_cpu"] = value / cb["value"]

@@ -1,6 +1,6 @@
 #!/bin/sh
 # Build-time extraction of the reference's own per-pair path functions into a
-# scratch directory OUTSIDE the repository (default /tmp/lqro_ref_extract, see
+# scratch directory OUTSIDE the repository (default /tmp/lqro_ref_extract_<uid>, see
 # Makefile), so that no reference source sits in the tree that is pushed to
 # the GPU box.  Used only to compile the
 # reference itself as an oracle (oracle/_ref/libref.so, see Makefile).

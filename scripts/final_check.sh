@@ -23,6 +23,6 @@ exit 0
 fi
 bash scripts/gpu_profile.sh $TAG > $O/profile.log 2>&1 || { tail -20 $O/profile.log; exit 1; }
 cp gpurun_out/${TAG}_* $O/ 2>/dev/null || true
-LQRO_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2ranks_gloo.json 2> $O/bench_2ranks_gloo.err || { tail -20 $O/bench_2ranks_gloo.err; exit 1; }
+LQRO_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2ranks_gloo.json 2> $O/bench_2ranks_gloo.err || { tail -20 $O/bench_2ranks_gloo.err; exit 1; }
 tail -c 300 $O/bench_2ranks_gloo.json
 echo final check done

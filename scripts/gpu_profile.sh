@@ -12,7 +12,7 @@ mkdir -p $O
 # the profiled command runs C3 only (--no-configs): C4 / C5 steps can take the
 # plain schedule, whose full-grid k_pair launches would otherwise be averaged
 # with the C3 roofline probe's (same grid)
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-configs"
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-configs"
 # the traffic passes first: their summary (stamped with this liblqro.so) goes
 # into profiles/ so that the bench line below cites it as roofline.traffic
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof_fetch -o run -- $B > $O/prof_fetch.log 2>&1
@@ -25,7 +25,7 @@ LQRO_QSIDE=0 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv 
 LQRO_QSIDE=0 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof_write_q -o run -- $B > $O/prof_write_q.log 2>&1
 python3 scripts/pmc_traffic.py $O/prof_fetch_q $O/prof_write_q $O/${TAG}_pmc_traffic_qhull.json > /dev/null
 cp $O/${TAG}_pmc_traffic_qhull.json profiles/${TAG}_pmc_traffic_qhull.json
-timeout -k 10 300 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+timeout -k 10 300 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt -o run -- $B > $O/prof_kt.log 2>&1
 python3 scripts/kernel_breakdown.py $O/prof_kt $O/${TAG}_kernel_breakdown.json > /dev/null
 python3 -c "import glob,shutil;shutil.copy(glob.glob('$O/prof_kt/**/*kernel_stats.csv',recursive=True)[0],'$O/${TAG}_kernel_stats.csv')"
