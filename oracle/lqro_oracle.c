@@ -1280,12 +1280,28 @@ static float fmins(float a, float b) { return (b < a) ? b : a; }  /* std::min */
  * orc_lp_chain: test instrumentation only, it does not change any result */
 static __thread long long g_lp_chain;
 
+/* how often the LP took each of its rarely met branches since the last
+ * orc_lp_branches (same kind of instrumentation: counters only).  The tests
+ * use them to prove that their plane sets still reach these branches. */
+enum {
+  LPB_LP1_DISC_NEG,    /* linearProgram1: discriminant < 0 */
+  LPB_LP1_PAR_REJECT,  /* linearProgram1: parallel plane rejects */
+  LPB_LP2_BEYOND,      /* linearProgram2: plane beyond the speed sphere */
+  LPB_LP2_DIR_SMALL,   /* linearProgram2: directionOpt, planeOptVelocityLengthSq <= eps */
+  LPB_LP2_PAR_FAIL,    /* linearProgram2: violated plane parallel to planeNo */
+  LPB_LP4_SAME_SKIP,   /* linearProgram4: same-direction parallel plane skipped */
+  LPB_LP4_ANTI_MID,    /* linearProgram4: antiparallel pair, midpoint plane */
+  LPB_LP4_INNER_FAIL,  /* linearProgram4: inner linearProgram3 fails */
+  LPB_COUNT
+};
+static __thread long long g_lp_branch[LPB_COUNT];
+
 static int lp1(const plane_t* planes, int planeNo, const line_t* line, float radius, v3 optVelocity,
                int directionOpt, v3* result) {
   g_lp_chain++;
   const float dotProduct = vdot(line->point, line->direction);
   const float discriminant = sqrf(dotProduct) + sqrf(radius) - vabsSq(line->point);
-  if (discriminant < 0.0f) return 0;
+  if (discriminant < 0.0f) { g_lp_branch[LPB_LP1_DISC_NEG]++; return 0; }
   const float sqrtDiscriminant = sqrtf(discriminant);
   float tLeft = -dotProduct - sqrtDiscriminant;
   float tRight = -dotProduct + sqrtDiscriminant;
@@ -1293,7 +1309,7 @@ static int lp1(const plane_t* planes, int planeNo, const line_t* line, float rad
     const float numerator = vdot(vsub(planes[i].point, line->point), planes[i].normal);
     const float denominator = vdot(line->direction, planes[i].normal);
     if (sqrf(denominator) <= RVO_EPSILON) {
-      if (numerator > 0.0f) return 0;
+      if (numerator > 0.0f) { g_lp_branch[LPB_LP1_PAR_REJECT]++; return 0; }
       else continue;
     }
     const float t = numerator / denominator;
@@ -1318,15 +1334,19 @@ static int lp2(const plane_t* planes, int planeNo, float radius, v3 optVelocity,
   const float planeDist = vdot(planes[planeNo].point, planes[planeNo].normal);
   const float planeDistSq = sqrf(planeDist);
   const float radiusSq = sqrf(radius);
-  if (planeDistSq > radiusSq) return 0;
+  if (planeDistSq > radiusSq) { g_lp_branch[LPB_LP2_BEYOND]++; return 0; }
   const float planeRadiusSq = radiusSq - planeDistSq;
   const v3 planeCenter = smul(planeDist, planes[planeNo].normal);
   if (directionOpt) {
     const v3 planeOptVelocity =
         vsub(optVelocity, smul(vdot(optVelocity, planes[planeNo].normal), planes[planeNo].normal));
     const float planeOptVelocityLengthSq = vabsSq(planeOptVelocity);
-    if (planeOptVelocityLengthSq <= RVO_EPSILON) *result = planeCenter;
-    else *result = vadd(planeCenter, smul(sqrtf(planeRadiusSq / planeOptVelocityLengthSq), planeOptVelocity));
+    if (planeOptVelocityLengthSq <= RVO_EPSILON) {
+      g_lp_branch[LPB_LP2_DIR_SMALL]++;
+      *result = planeCenter;
+    } else {
+      *result = vadd(planeCenter, smul(sqrtf(planeRadiusSq / planeOptVelocityLengthSq), planeOptVelocity));
+    }
   } else {
     *result = vadd(optVelocity, smul(vdot(vsub(planes[planeNo].point, optVelocity), planes[planeNo].normal),
                                      planes[planeNo].normal));
@@ -1340,7 +1360,7 @@ static int lp2(const plane_t* planes, int planeNo, float radius, v3 optVelocity,
     if (vdot(planes[i].normal, vsub(planes[i].point, *result)) > 0.0f) {
       g_lp_chain++;
       v3 crossProduct = vcross(planes[i].normal, planes[planeNo].normal);
-      if (vabsSq(crossProduct) <= RVO_EPSILON) return 0;
+      if (vabsSq(crossProduct) <= RVO_EPSILON) { g_lp_branch[LPB_LP2_PAR_FAIL]++; return 0; }
       line_t line;
       line.direction = vnormalize(crossProduct);
       const v3 lineNormal = vcross(line.direction, planes[planeNo].normal);
@@ -1383,8 +1403,13 @@ static void lp4(const plane_t* planes, int m, int beginPlane, float radius, v3* 
         plane_t plane;
         const v3 crossProduct = vcross(planes[j].normal, planes[i].normal);
         if (vabsSq(crossProduct) <= RVO_EPSILON) {
-          if (vdot(planes[i].normal, planes[j].normal) > 0.0f) continue;
-          else plane.point = smul(0.5f, vadd(planes[i].point, planes[j].point));
+          if (vdot(planes[i].normal, planes[j].normal) > 0.0f) {
+            g_lp_branch[LPB_LP4_SAME_SKIP]++;
+            continue;
+          } else {
+            g_lp_branch[LPB_LP4_ANTI_MID]++;
+            plane.point = smul(0.5f, vadd(planes[i].point, planes[j].point));
+          }
         } else {
           const v3 lineNormal = vcross(crossProduct, planes[i].normal);
           plane.point = vadd(planes[i].point,
@@ -1396,7 +1421,10 @@ static void lp4(const plane_t* planes, int m, int beginPlane, float radius, v3* 
         scratch[np++] = plane;
       }
       const v3 tempResult = *result;
-      if (lp3(scratch, np, radius, planes[i].normal, 1, result) < np) *result = tempResult;
+      if (lp3(scratch, np, radius, planes[i].normal, 1, result) < np) {
+        g_lp_branch[LPB_LP4_INNER_FAIL]++;
+        *result = tempResult;
+      }
       distance = vdot(planes[i].normal, vsub(planes[i].point, *result));
     }
   }
@@ -1437,6 +1465,12 @@ long long orc_lp_chain(int m, const float* pl, const double* vgoal, double vmax_
   c0 = g_lp_chain;
   orc_newv(m, pl, vgoal, vmax_lp, nv);
   return g_lp_chain - c0;
+}
+
+/* the calling thread's branch counts (LPB_* order, LPB_COUNT = 8 entries)
+ * since its last call; resets them */
+void orc_lp_branches(long long* out) {
+  for (int k = 0; k < LPB_COUNT; k++) { out[k] = g_lp_branch[k]; g_lp_branch[k] = 0; }
 }
 
 /* operator! on a 3x3 / 4x4 matrix (MAT:603-671), for the tests */

@@ -50,6 +50,7 @@ def lib():
         _o.orc_newv.argtypes = [C.c_int, C.c_void_p, C.c_void_p, d, C.c_void_p]
         _o.orc_lp_chain.argtypes = [C.c_int, C.c_void_p, C.c_void_p, d]
         _o.orc_lp_chain.restype = C.c_longlong
+        _o.orc_lp_branches.argtypes = [C.c_void_p]
         _o.orc_sphere.argtypes = [C.c_int, d, d, C.c_void_p]
         _o.orc_pinv.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         _o.orc_hull_branch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -201,6 +202,20 @@ def lp_chain(planes6: np.ndarray, vgoal, vmax_lp=100.0) -> int:
     planes6 = np.ascontiguousarray(planes6, np.float32).reshape(-1, 6)
     v = np.ascontiguousarray(vgoal, np.float64)
     return int(lib().orc_lp_chain(planes6.shape[0], _p(planes6), _p(v), vmax_lp))
+
+
+# orc_lp_branches' order (LPB_* in lqro_oracle.c)
+LP_BRANCHES = ("lp1 discriminant < 0", "lp1 parallel reject", "lp2 beyond sphere",
+               "lp2 directionOpt small", "lp2 parallel fail", "lp4 same-direction skip",
+               "lp4 antiparallel midpoint", "lp4 inner lp3 fails")
+
+
+def lp_branches() -> dict:
+    """How often this thread's newv()/step() calls took each of the LP's rare
+    branches since the last call (read and reset)."""
+    out = np.zeros(len(LP_BRANCHES), np.int64)
+    lib().orc_lp_branches(_p(out))
+    return dict(zip(LP_BRANCHES, (int(v) for v in out)))
 
 
 def round6(v: float) -> float:

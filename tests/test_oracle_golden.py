@@ -103,6 +103,60 @@ def test_newv_c3_hardest_rows(oracle):
         assert oracle.lp_chain(d["planes"][k], d["vgoal"][k], float(d["vmax_lp"])) == d["chain"][k]
 
 
+def test_lp_edge_cases_reach_rare_branches(oracle):
+    """The directed LP families (lp_cases.edge_cases) are there for eight
+    branches of linearProgram1-4 that random unit normals do not reach.  The
+    oracle counts them (pyoracle.lp_branches): at least 5 of each over the
+    whole set, at least one of each over the rows that test_gpu_lp runs under
+    every plane layout (each family's first repetition), and every result
+    finite.  A count that falls short means the generator changed: change
+    its seed or mix, not these bounds."""
+    import lp_cases
+    cases, goals, names = lp_cases.edge_cases(lp_cases.EDGE_REPS)
+    assert len(cases) == len(lp_cases.FAMILIES) * lp_cases.EDGE_REPS * len(lp_cases.EDGE_SIZES)
+    first = lp_cases.edge_first_rep(lp_cases.EDGE_REPS)
+    assert [names[i] for i in first] == [f for f in lp_cases.FAMILIES for _ in lp_cases.EDGE_SIZES]
+    assert [len(cases[i]) for i in first] == list(lp_cases.EDGE_SIZES) * len(lp_cases.FAMILIES)
+    oracle.lp_branches()
+    for c, g in zip(cases, goals):
+        assert np.isfinite(c).all() and np.isfinite(g).all()
+        assert np.isfinite(oracle.newv(c, g)).all()
+    counts = oracle.lp_branches()
+    print("edge_cases:", counts)
+    assert list(counts) == list(oracle.LP_BRANCHES)
+    assert all(v >= 5 for v in counts.values()), counts
+    for i in first:
+        oracle.newv(cases[i], goals[i])
+    counts = oracle.lp_branches()
+    print("first repetition:", counts)
+    assert all(v >= 1 for v in counts.values()), counts
+    assert not any(oracle.lp_branches().values())   # read and reset
+
+
+def test_newv_lp_edges(oracle):
+    """lp_edges.npz (the reference's calculateNewV on the directed families, on
+    rows with subnormal coordinates and on the long rows at the plane-layout
+    switches, make_golden_lp_edges.py):
+    the generator still makes the fixture's rows, and the oracle reproduces
+    every new velocity bit for bit."""
+    import lp_cases
+    d = _load("lp_edges.npz")
+    cases, goals, names = lp_cases.fixture_rows()
+    offs = d["offsets"]
+    assert len(cases) == d["newv"].shape[0] == offs.size - 1
+    assert _same_bits(np.concatenate(cases), d["planes"]) and _same_bits(goals, d["vgoal"])
+    assert [str(d["families"][f]) for f in d["family"]] == names
+    for k, (c, g) in enumerate(zip(cases, goals)):
+        assert _same_bits(c, d["planes"][offs[k]:offs[k + 1]])
+        assert _same_bits(oracle.newv(c, g), d["newv"][k]), (k, names[k], len(c))
+    assert tuple(d["long_m"]) == lp_cases.LONG_SIZES
+    for k, m in enumerate(d["long_m"]):
+        c, g = lp_cases.long_row(int(m), int(d["long_seed"][k]))
+        assert len(c) == m
+        assert lp_cases.digest(c, g) == str(d["long_sha"][k]), f"long_row({m}) is not the fixture's row"
+        assert _same_bits(oracle.newv(c, g), d["long_newv"][k]), m
+
+
 @pytest.mark.parametrize("scenario", ["c2", "swap"])
 def test_row_newv_bit_exact(oracle, scenario):
     """The whole row body (LQRO:1393-1435) for the golden rows."""

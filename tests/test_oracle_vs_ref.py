@@ -95,6 +95,20 @@ def test_newv_random(oracle, ref):
         assert np.array_equal(_bits(oracle.newv(c, v)), _bits(out))
 
 
+def test_newv_edge_families(oracle, ref):
+    """The directed LP families (parallel and nearly parallel planes, planes
+    at the speed limit, zero normals, subnormal squares) with a seed other
+    than the fixture's."""
+    from lp_cases import edge_cases
+    cases, goals, names = edge_cases(2, seed=2024)
+    for k, (c, v) in enumerate(zip(cases, goals)):
+        c = np.ascontiguousarray(c, np.float32)
+        v = np.ascontiguousarray(v, np.float64)
+        out = np.zeros(3)
+        ref.ref_newv(c.shape[0], _p(c), _p(v), _p(out))
+        assert np.array_equal(_bits(oracle.newv(c, v)), _bits(out)), (k, names[k], c.shape[0])
+
+
 def test_inverse_matches_reference(oracle, ref):
     """operator! (MAT:603-671) via the gain synthesis: covered bit-exactly by
     test_oracle_golden.test_gains_bit_exact; here the 3x3 inverse the tables
