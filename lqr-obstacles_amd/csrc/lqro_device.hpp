@@ -19,13 +19,87 @@ constexpr int kWave = 64;
 // queues, -1 for each hot pair done without a hull and each hull job done:
 // it equals row_split * LQRO_ROW_BIG exactly when the row has nothing open.
 #define LQRO_ROW_BIG (1 << 20)
+
+// ---------------------------------------------------------------------------
+// The words of the counter blocks that the kernels and the runtime share
+// ---------------------------------------------------------------------------
+// The step's counters (the context's d_stats, zeroed per step): [0..7]
+// lqro_get_stats' words, [8..11] lqro_get_stats_ex's:
+#define LQRO_ST_PAIRS 0     // pairs (culling on: k_nbr counts the kept ones)
+#define LQRO_ST_PLANES 1    // half-planes emitted
+#define LQRO_ST_INSIDE 2    // inside-hull pairs (the next steps' schedule reads it, StepFeedback)
+#define LQRO_ST_HULLOK 3    // inside-hull pairs whose hull gave the plane
+#define LQRO_ST_HULLFAIL 4  // ... left without their half-plane (LQRO_E_HULL)
+#define LQRO_ST_BACKUP 5    // GJK backup procedures
+#define LQRO_ST_NREACH 6    // sum of n_reach
+#define LQRO_ST_GTESTS 7    // sum of G-tests (GJK iterations)
+#define LQRO_ST_MERGED 8    // Qhull-order hulls Qhull would merge facets in (LQRO_REC_QHMERGE)
+#define LQRO_ST_RETRY 9     // builds k_qhull's caps handed to k_qhull_big
+#define LQRO_ST_TIMEOUT 10  // k_qhull wave-handshake timeouts (the build went to k_qhull_big)
+#define LQRO_ST_NFAIL 11    // pairs left without their half-plane, the first LQRO_ST_FAILMAX of their slots in [16 ..]
+#define LQRO_ST_MWIN 12     // pairs flagged LQRO_REC_QHMERGE_WIN (lqro_get_stats_ex [11])
+#define LQRO_ST_NBUILD 13   // Qhull-order build records written (HullArgs::hbuild)
+#define LQRO_ST_FAILS 16
+#define LQRO_ST_FAILMAX 64
+#define LQRO_ST_MWINS (LQRO_ST_FAILS + LQRO_ST_FAILMAX)   // the first LQRO_ST_FAILMAX MWIN slots
 // The step's work, for the next steps' schedule (the side's width): the
 // sweep's workgroup time summed over k_pair's workgroups (one a CU), the
 // Qhull-order builds' time summed and their maximum, on the 100 MHz clock
-// (s_memrealtime); words of the context's stats array (lqro_hull.hpp)
-#define LQRO_ST_SWORK 144
-#define LQRO_ST_BWORK 145
-#define LQRO_ST_BMAX 146
+// (s_memrealtime)
+#define LQRO_ST_SWORK (LQRO_ST_MWINS + LQRO_ST_FAILMAX)   // 144: the work words follow the named pairs
+#define LQRO_ST_BWORK (LQRO_ST_SWORK + 1)
+#define LQRO_ST_BMAX (LQRO_ST_SWORK + 2)
+#define LQRO_ST_WORDS (LQRO_ST_SWORK + 4)
+
+// The queue counters (the context's d_hcount, 16 ints zeroed per step): each
+// queue's count, and the head its consumers advance
+enum : int {
+  LQRO_HC_HULL = 0,       // the hull queue (PairArgs::hull_count, HullArgs::count); k_prio_prev presets
+  LQRO_HC_HULL_NEXT = 1,  //   both for the speculative builds
+  LQRO_HC_RETRY = 2,      // jobs past the LDS hull's / k_qhull's caps (HullArgs::rcount)
+  LQRO_HC_RETRY_NEXT = 3,
+  LQRO_HC_ROW = 4,        // k_pair's row queue (PairArgs::row_counter)
+  LQRO_HC_UNUSED5 = 5,
+  LQRO_HC_HOT = 6,        // k_prio's hot list
+  LQRO_HC_HOT_NEXT = 7,
+  LQRO_HC_UNUSED8 = 8,
+  LQRO_HC_LP4 = 9,        // k_lp_lds -> k_lp4 row list
+  LQRO_HC_LP4_NEXT = 10,
+  LQRO_HC_LHAND = 11,     // pairs k_lhull handed to the full hull (HullArgs::lcount)
+  LQRO_HC_LHAND_NEXT = 12,
+  LQRO_HC_LDONE = 13,     // pairs k_lhull decided
+  LQRO_HC_UNUSED14 = 14,
+  LQRO_HC_FACET0 = 15,    // Qhull order: slots whose facet 0 won (k_stale's list, HullArgs::qstale_count)
+  LQRO_HC_WORDS = 16
+};
+
+// Qhull order, the split hot launch's counters (the context's d_hot2;
+// [1..6] zeroed per split step, [0] carried from step to step)
+enum : int {
+  LQRO_H2_PREV = 0,        // the last step's inside-hull pairs (k_prio_save -> k_prio_prev)
+  LQRO_H2_HOT1 = 1,        // the first hot launch's pair count
+  LQRO_H2_HOT1_NEXT = 2,   // ... and its head
+  LQRO_H2_HOT2_NEXT = 3,   // the second (main stream) hot launch's head
+  LQRO_H2_HOT2_DONE = 4,   // ... and its finished workgroups (PairArgs::hot_done)
+  LQRO_H2_SPEC = 5,        // speculative builds queued at the step's start
+  LQRO_H2_SPEC_NEXT = 6,   // ... and the ticket that hands them out
+  LQRO_H2_UNUSED7 = 7,
+  LQRO_H2_WORDS = 8
+};
+
+// The profile words (the context's d_prof, cumulative; the lqro_debug_*
+// calls read them): each region's first word
+enum : int {
+  LQRO_PROF_HULL = 0,                               // 32 hull counters
+  LQRO_PROF_HJOBS = LQRO_PROF_HULL + 32,            // 2 words per hull job (< 4096)
+  LQRO_PROF_PAIR = LQRO_PROF_HJOBS + 2 * 4096,      // k_pair's 16 phase words, then 16 hull wave phases
+  LQRO_PROF_LFAIL = LQRO_PROF_PAIR + 16 + 16,       // k_lhull's 16 hand-over reasons
+  LQRO_PROF_LJOBS = LQRO_PROF_LFAIL + 16,           // k_lhull's 4 words per job (< 4096)
+  LQRO_PROF_QW1 = LQRO_PROF_LJOBS + 4 * 4096,       // k_qhull's wave 1 (Q3_PROF_W1), 64 words
+  LQRO_PROF_QLONG = LQRO_PROF_QW1 + 64,             // LQRO_QHULL_LONGPROF: 24 x 1024
+  LQRO_PROF_WORDS = LQRO_PROF_QLONG + 24 * 1024,
+  LQRO_PROF_HULL_WORDS = LQRO_PROF_LFAIL            // what lqro_debug_hull_profile returns
+};
 
 // Workgroup-scope fence pair: orders this wave's LDS writes before other
 // lanes' later reads (LDS executes a wave's instructions in order; this keeps

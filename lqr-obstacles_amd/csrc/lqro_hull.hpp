@@ -271,30 +271,15 @@ struct HullLdsC {
 // the compiler has to be kept from moving memory operations across this
 // point; no s_waitcnt / s_barrier is needed (a workgroup fence would stall on
 // every outstanding global store).
-// The step's counters (lqro_get_stats_ex): [0..7] lqro_get_stats' words;
-// [8] Qhull-order hulls Qhull would merge facets in (LQRO_REC_QHMERGE);
-// [9] builds k_qhull's caps handed to k_qhull_big; [10] k_qhull wave-handshake
-// timeouts (the build went to k_qhull_big); [11] pairs left without their
-// half-plane, the first LQRO_ST_FAILMAX of their slots in [16 ..]
-#define LQRO_ST_MERGED 8
-#define LQRO_ST_RETRY 9
-#define LQRO_ST_TIMEOUT 10
-#define LQRO_ST_NFAIL 11
-#define LQRO_ST_MWIN 12     // pairs flagged LQRO_REC_QHMERGE_WIN (lqro_get_stats_ex [11])
+// (the step's counters, LQRO_ST_*: lqro_device.hpp)
 #define LQRO_QHMERGE_K 1024.0   // the merge-suspect test's reach, x qh DISTround (q3_merge_suspect)
-#define LQRO_ST_NBUILD 13   // Qhull-order build records written (A.hbuild)
 #define LQRO_HBUILD_CAP 16384
-#define LQRO_ST_FAILS 16
-#define LQRO_ST_FAILMAX 64
-#define LQRO_ST_MWINS (LQRO_ST_FAILS + LQRO_ST_FAILMAX)   // the first LQRO_ST_FAILMAX MWIN slots
-#define LQRO_ST_WORDS (LQRO_ST_MWINS + LQRO_ST_FAILMAX + 4)   // + LQRO_ST_SWORK, _BWORK, _BMAX (lqro_device.hpp)
-static_assert(LQRO_ST_SWORK == LQRO_ST_MWINS + LQRO_ST_FAILMAX, "the work words follow the named pairs");
 
 // an inside-hull pair left without its half-plane (a hull capacity): counted
-// in stats[4] and named, so the step reports it (LQRO_E_HULL) instead of
+// in LQRO_ST_HULLFAIL and named, so the step reports it (LQRO_E_HULL) instead of
 // dropping the constraint silently
 __device__ __forceinline__ void hull_fail_note(unsigned long long* stats, int slot) {
-  atomicAdd(&stats[4], 1ull);
+  atomicAdd(&stats[LQRO_ST_HULLFAIL], 1ull);
   const unsigned long long k = atomicAdd(&stats[LQRO_ST_NFAIL], 1ull);
   if (k < LQRO_ST_FAILMAX) stats[LQRO_ST_FAILS + k] = (unsigned long long)slot;
 }
@@ -746,7 +731,7 @@ __device__ __forceinline__ void hull_select(const HullArgs& A, const Mem& M, LT&
       pl[2] = (float)(xi[5] + mult * dh * nrm[2]);
       pl[3] = (float)nrm[0]; pl[4] = (float)nrm[1]; pl[5] = (float)nrm[2];
       pl[6] = __int_as_float(1);
-      atomicAdd(&A.stats[3], 1ull);
+      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
     } else {
       pl[6] = __int_as_float(0);                         // no usable plane
       hull_fail_note(A.stats, slot);
@@ -1512,14 +1497,14 @@ __device__ __forceinline__ void hull_insert_mw(HullMemC& M, HullLdsC<NW>& L, con
   }
 #ifdef LQRO_HULL_PROFILE
   if (lane == 0 && pstat)
-    for (int k = 0; k < 12; ++k) atomicAdd(&pstat[32 + 2 * 4096 + 16 - 10 + k], wacc[k]);
+    for (int k = 0; k < 12; ++k) atomicAdd(&pstat[LQRO_PROF_PAIR + 16 - 10 + k], wacc[k]);
   if (lane == 0 && pstat) {
     atomicAdd(&pstat[0], n_ins);
     atomicAdd(&pstat[1], n_conf);
     atomicAdd(&pstat[2], n_stale);
     atomicMax(&pstat[3], (unsigned long long)maxr);
     atomicAdd(&pstat[4], n_big);
-    atomicAdd(&pstat[32 + 2 * 4096 + 16 - 10 + 15], n_held);
+    atomicAdd(&pstat[LQRO_PROF_PAIR + 16 - 10 + 15], n_held);
   }
 #else
   (void)n_ins; (void)n_conf; (void)n_stale; (void)pstat; (void)maxr; (void)n_big; (void)n_held;

@@ -885,7 +885,11 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
     unsigned long long sum = 0;
     for (int w = 0; w < nw; ++w)
       sum += reinterpret_cast<const unsigned long long*>(lds + P.lds_wave + (size_t)w * P.wave_doubles + st_off)[threadIdx.x];
-    const int dst = threadIdx.x == 0 ? 6 : threadIdx.x == 1 ? 7 : threadIdx.x == 2 ? 1 : threadIdx.x == 3 ? 2 : 5;
+    const int dst = threadIdx.x == 0   ? LQRO_ST_NREACH
+                    : threadIdx.x == 1 ? LQRO_ST_GTESTS
+                    : threadIdx.x == 2 ? LQRO_ST_PLANES
+                    : threadIdx.x == 3 ? LQRO_ST_INSIDE
+                                       : LQRO_ST_BACKUP;
     if (sum) atomicAdd(&P.stats[dst], sum);
   }
   if (threadIdx.x == 64) atomicAdd(&P.stats[LQRO_ST_SWORK], __builtin_amdgcn_s_memrealtime() - t_wg);
@@ -916,7 +920,7 @@ __global__ void __launch_bounds__(LQRO_PAIR_LB) k_pair(PairArgs P) {
 // the set RVO2's sorted insertion keeps when agents are visited in j order.
 // Found by k rounds of a wave arg-min above the previous key; writes the
 // row's list of K = min(k, npr) slots (neighbour jj ascending, -1 padded)
-// and counts the kept pairs into stats[0].
+// and counts the kept pairs into LQRO_ST_PAIRS.
 __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int row_begin, int row_stride, int npr,
                                             double r2,
                                             int k, int K, int* list, unsigned long long* stats) {
@@ -1008,7 +1012,7 @@ __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int r
     cnt += __popcll(bal);
   }
   for (int q = cnt + lane; q < K; q += 64) row[q] = -1;
-  if (lane == 0) atomicAdd(&stats[0], (unsigned long long)taken);
+  if (lane == 0) atomicAdd(&stats[LQRO_ST_PAIRS], (unsigned long long)taken);
 }
 
 // k_prio: which pairs go first.  A pair whose relative motion brings the two
@@ -1062,8 +1066,8 @@ __global__ void __launch_bounds__(256) k_prio_prev(PrioArgs A) {
     *A.hot1n = m;
     *A.hot2next = A.hq ? 0 : m;
     if (A.hq) {
-      A.hcount[0] = m;   // the queue's count
-      A.hcount[1] = m;   // its head, past the entries handed out by spec_next
+      A.hcount[LQRO_HC_HULL] = m;   // the queue's count
+      A.hcount[LQRO_HC_HULL_NEXT] = m;   // its head, past the entries handed out by spec_next
       *A.spec_n = m;
     }
   }

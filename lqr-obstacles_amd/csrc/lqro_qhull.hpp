@@ -1381,13 +1381,13 @@ __device__ inline void qh_select(const HullArgs& A, const QhW& W, const QhS& S, 
       pl[3] = (float)nrm[0]; pl[4] = (float)nrm[1]; pl[5] = (float)nrm[2];
       pl[6] = __int_as_float(1);
       qn[0] = nrm[0]; qn[1] = nrm[1]; qn[2] = nrm[2]; qn[3] = best;
-      atomicAdd(&A.stats[3], 1ull);
+      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
     } else if (stale) {
       pl[6] = __int_as_float(3);                         // pending: the loop-carried normal (k_stale)
       qn[0] = qn[1] = qn[2] = 0.0; qn[3] = best;
       const int k = atomicAdd(A.qstale_count, 1);
       if (k < A.qstale_cap) A.qstale[k] = slot;
-      atomicAdd(&A.stats[3], 1ull);
+      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
     } else {
       pl[6] = __int_as_float(0);
       hull_fail_note(A.stats, slot);

@@ -62,7 +62,7 @@ namespace lqro {
 #ifndef Q3_FL
 #define Q3_FL 2240        // facet slots with their hot fields in LDS (the rest of 160 KB)
 #endif
-#define Q3_PROF_RETRY (32 + 2 * 4096 + 16)   // profile words: builds handed to k_qhull_big (16)
+#define Q3_PROF_RETRY (LQRO_PROF_PAIR + 16)   // profile words: builds handed to k_qhull_big (16)
 #ifdef LQRO_QHULL_PROFILE
 #define Q3_CAPBIT(b) (b)   // which cap sent a build to k_qhull_big (scripts/qhull_prof.py)
 #else
@@ -308,7 +308,7 @@ struct Q3S {
 // 10 waits; 16 + k: wave 0's phase k (Q3T) over the insertions whose partition
 // sequence fits one chunk (np <= 64), 40 their number; cycles summed over the
 // step's hulls (lqro_debug_prof_words)
-#define Q3_PROF_W1 (32 + 2 * 4096 + 48 + 4 * 4096)
+#define Q3_PROF_W1 LQRO_PROF_QW1
 // LQRO_QHULL_LONGPROF (a diagnostic build, scripts/build_variant.sh): per
 // build record k (lqro_get_hull_builds order, k < 1024), prof words
 // Q3_PROF_LONG + 24 k: insertions whose partition sequence is longer than one
@@ -320,7 +320,7 @@ struct Q3S {
 // waiting for them, ticks stopping them, events, posts; helper chunks and
 // their ticks; wave 1's speculations, publication -> seen and seen -> done
 // ticks; wave 0's waits and their speculation-end -> seen ticks
-#define Q3_PROF_LONG (Q3_PROF_W1 + 64)
+#define Q3_PROF_LONG LQRO_PROF_QLONG
 struct Q3P {
   unsigned long long tq2 = 0;   // LQRO_QHULL_PROFILE: the last speculation's end (this wave's clock)
   unsigned long long t[16];
@@ -3193,13 +3193,13 @@ __device__ inline bool q3_select(const HullArgs& A, const Q3W& W, const Q3L& L, 
       pl[3] = (float)nrm[0]; pl[4] = (float)nrm[1]; pl[5] = (float)nrm[2];
       pl[6] = __int_as_float(1);
       qn[0] = nrm[0]; qn[1] = nrm[1]; qn[2] = nrm[2]; qn[3] = best;
-      atomicAdd(&A.stats[3], 1ull);
+      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
     } else if (stale) {
       pl[6] = __int_as_float(3);                         // pending: the loop-carried normal (k_stale)
       qn[0] = qn[1] = qn[2] = 0.0; qn[3] = best;
       const int k = atomicAdd(A.qstale_count, 1);
       if (k < A.qstale_cap) A.qstale[k] = slot;
-      atomicAdd(&A.stats[3], 1ull);
+      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
     } else {
       pl[6] = __int_as_float(0);
       hull_fail_note(A.stats, slot);

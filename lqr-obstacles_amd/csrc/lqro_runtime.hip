@@ -30,17 +30,13 @@
 
 #include "../../include/lqro.h"
 #include "lqro_device.hpp"
+#include "lqro_plan.hpp"
 #include "lqro_lp.hpp"
 #include "lqro_pair_launch.hpp"
 #include "lqro_hull.hpp"
 #include "lqro_synth.hpp"
 #include "lqro_dyn.hpp"
 #include "lqro_kern.hpp"
-
-// hull: 32 counters + 2 words per job; pair: 16; hull wave phases: 16; local hull hand-overs: 16;
-// local-hull per-job words 4 x 4096
-#define LQRO_PROF_WORDS (32 + 2 * 4096 + 16 + 16 + 16 + 4 * 4096 + 64 + 24 * 1024)   // + 64: k_qhull's wave 1 (Q3_PROF_W1); + 24 x 1024: LQRO_QHULL_LONGPROF
-#define LQRO_PROF_HULL_WORDS (32 + 2 * 4096 + 32)   // what lqro_debug_hull_profile returns
 
 using namespace lqro;
 
@@ -383,48 +379,28 @@ struct lqro_ctx {
   double *d_A, *d_B, *d_L, *d_E;
   float *d_planes, *d_lpscratch, *d_lpcompact;
   lqro_pair_record* d_recs;
-  int *d_hq, *d_hcount, *d_hnext, *d_err, *d_rq;
+  int *d_hq, *d_hcount, *d_err, *d_rq;   // d_hcount: LQRO_HC_* (lqro_device.hpp)
   void* d_hbig;
   HullWide* d_hwide;
   int* d_hbag;
   int* d_lp4;                // k_lp_lds -> k_lp4 row list (6 ints per row)
   int* d_hotlist;            // k_prio: likely inside-hull pairs (slots), computed first
   int* d_prevq;              // Qhull order: the last step's inside-hull pairs (k_prio_save), hot_cap
-  int* d_hot2;               // [0] their count, [1] first hot launch's count, [2] its next, [3] the
-                             // second's next, [4] its finished workgroups
-  int hot_split;             // LQRO_HOT_SPLIT (default 1): the split hot launch in Qhull order
-  int qside_pct;             // LQRO_QHULL_SIDE_PCT: side CUs per 100 of the last step's inside-hull pairs (default 100)
-  int qhull_inline;          // LQRO_QHULL_INLINE_BIG: k_qhull rebuilds a capped build in place (default 1)
-  int qhull_flags;           // LQRO_QHULL_FLAGS: k_qhull's helper waves (1), emit lane state (2), queue pre-scan (4),
-                             // a long emit over the waves (16); default 23
-  int qbalance;              // LQRO_QHULL_BALANCE: the side's width from the measured work (default 1)
-  int qspare;                // LQRO_QHULL_SPARE: side CUs beyond the last step's inside-hull count (default 4; -1: count/16 + 4)
-  int hot_spec;              // LQRO_HOT_SPEC (default 1): with the split, the last step's inside pairs are built speculatively from the step's start
+  int* d_hot2;               // the split hot launch's counters: LQRO_H2_* (lqro_device.hpp)
+  StepKnobs knobs;           // the environment knobs (lqro_plan.hpp)
   unsigned char* d_hotmark;  // per slot: in the hot list
   int* d_nbrlist;            // culling on: per row K neighbour slots (lqro_set_neighbors)
   double nbr_r2;
   int nbr_k, nbr_cap;         // k; rows x nbr_cap ints allocated
   int hot_cap;
-  int hot_on;                // LQRO_HOT (default 1)
-  int hull_big_only;         // LQRO_HULL_BIG: skip the LDS hull (A/B)
-  int local_hull;            // LQRO_LOCAL_HULL (default 1): k_lhull first, k_hull for what it hands over
   int* d_lq;                 // k_lhull -> k_hull queue
-  int lside_cus;             // side CUs with the local hull (LQRO_LOCAL_SIDE_CUS, default 3/16 of the CUs)
-  double hot_t, hot_r;       // k_prio horizon (s) and radius (m): LQRO_HOT_T, LQRO_HOT_R
-  // inside-hull pairs of an earlier step (pinned, copied at the end of each
-  // step; ~0 = none yet) size the side stream: beyond 2 per side CU it widens
-  // by a third (at most half the CUs), beyond 4 per (widened) side CU the
-  // side CUs cannot keep up with the hulls and the plain schedule (every CU
-  // on the hulls after the sweep) is faster (scripts/crowded.py)
-  unsigned long long* h_inside;   // 2 pinned slots of 8 words: step t writes slot t & 1: inside-hull
-                                  //   pairs, then LQRO_ST_SWORK, _BWORK, _BMAX (100 MHz ticks),
-                                  //   then LQRO_ST_RETRY (builds past k_qhull's caps)
+  // what each step leaves for the schedule of the step two after it (pinned,
+  // copied at the end of the step): step t writes slot t & 1
+  StepFeedback* h_feedback;
   hipEvent_t iev[2];              // recorded after the copy into slot k
   long long nstep;                // steps enqueued
-  long hot_max_inside;       // LQRO_HOT_MAX_INSIDE (-1: 4 x the side CUs)
   int hull_big_blocks;
   int n_cu;
-  int side_cus;              // CUs running k_hull beside k_pair (LQRO_SIDE_HULL_CUS)
   double* d_hscratch;
   int* d_hiscratch;
   float* d_hfscratch;
@@ -440,11 +416,9 @@ struct lqro_ctx {
   const double* pend_x;
   const double* pend_vgoal;
   hipStream_t pend_stream;
-  int lhull_prof;            // LQRO_LHULL_PROFILE: k_lhull writes its per-job words
   // LQRO_FLAG_QHULL_ORDER: k_qhull workers, per-slot normals, facet-0 slots,
   // the loop-carried normal in [0..2], out [3..5]
   int qhull_order;
-  int qhull_big;            // LQRO_QHULL_BIG=1: every pair in k_qhull_big (A/B runs)
   int qworkers;
   size_t qstride;
   char* d_qscratch;
@@ -452,12 +426,9 @@ struct lqro_ctx {
   int* d_qstale;
   unsigned long long* d_hbuild;   // LQRO_HBUILD_CAP x 4 words: the builds' timing records
   double* d_carry;
-  // early LP (LQRO_EARLY_LP, default 1): per row open work and LP claim
-  // (lqro_hull.hpp hull_row_done)
-  int early_lp;
+  // early LP: per row open work and LP claim (lqro_hull.hpp hull_row_done)
   int early_step;            // the step being enqueued runs the early LP
   int early_internal;        // ... into d_newv (lqro_step_device_begin: the caller's buffer comes with _end)
-  int qside;                 // LQRO_QSIDE=1: k_qhull side workers sweep rows after their builds (default off)
   int* d_rowpend;
   int* d_rowclaim;
   PairArgs pa;
@@ -526,7 +497,7 @@ void lqro_destroy(lqro_ctx* c) {
   (void)hipSetDevice(c->cfg.device);
   void* ps[] = {c->d_R, c->d_TF, c->d_shash, c->d_T, c->d_NCF, c->d_S, c->d_x, c->d_vgoal, c->d_newv, c->d_A, c->d_B,
                 c->d_L, c->d_E, c->d_planes, c->d_lpscratch, c->d_lpcompact, c->d_recs, c->d_hq, c->d_hcount,
-                c->d_err, c->d_hfaces, /* d_hnext points into d_hcount */ c->d_hscratch, c->d_hiscratch, c->d_hfscratch, c->d_stats, c->d_prof, c->d_rq, c->d_hbig, c->d_hwide, c->d_hbag, c->d_lp4, c->d_hotlist, c->d_hotmark, c->d_nbrlist, c->d_hfbest, c->d_hvpid, c->d_hstack, c->d_lq,
+                c->d_err, c->d_hfaces, c->d_hscratch, c->d_hiscratch, c->d_hfscratch, c->d_stats, c->d_prof, c->d_rq, c->d_hbig, c->d_hwide, c->d_hbag, c->d_lp4, c->d_hotlist, c->d_hotmark, c->d_nbrlist, c->d_hfbest, c->d_hvpid, c->d_hstack, c->d_lq,
                 c->d_qscratch, c->d_qnrm, c->d_qstale, c->d_hbuild, c->d_carry, c->d_rowpend /* d_rowclaim inside */,
                 c->d_prevq, c->d_hot2};
   for (void* p : ps)
@@ -537,7 +508,7 @@ void lqro_destroy(lqro_ctx* c) {
     if (c->xev[k]) (void)hipEventDestroy(c->xev[k]);
     if (c->iev[k]) (void)hipEventDestroy(c->iev[k]);
   }
-  if (c->h_inside) (void)hipHostFree(c->h_inside);
+  if (c->h_feedback) (void)hipHostFree(c->h_feedback);
   if (c->side) (void)hipStreamDestroy(c->side);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -573,16 +544,13 @@ static int ctx_alloc(lqro_ctx* c) {
   // queue cannot overflow (C5's 2048 x 16383-slot shard: 134 MB, of 288 GB)
   c->hull_cap = (int)(slots > 0 ? slots : 1);
   HIPCHK(hipMalloc(&c->d_hq, sizeof(int) * c->hull_cap));
-  // hull count, next, retry count, retry next, pair rows, -, hot count, hot next, -, lp4 count, lp4 next,
-  // local-hull hand-over count, its next, local-hull decided
-  HIPCHK(hipMalloc(&c->d_hcount, sizeof(int) * 16));
-  c->d_hnext = c->d_hcount + 1;
+  HIPCHK(hipMalloc(&c->d_hcount, sizeof(int) * LQRO_HC_WORDS));
   HIPCHK(hipMalloc(&c->d_rq, sizeof(int) * c->hull_cap));
   HIPCHK(hipMalloc(&c->d_lq, sizeof(int) * c->hull_cap));
   HIPCHK(hipMalloc(&c->d_err, sizeof(int)));
   HIPCHK(hipMalloc(&c->d_stats, sizeof(unsigned long long) * LQRO_ST_WORDS));
-  HIPCHK(hipHostMalloc((void**)&c->h_inside, 16 * sizeof(unsigned long long), hipHostMallocDefault));
-  for (int k = 0; k < 16; ++k) c->h_inside[k] = k % 8 ? 0ull : ~0ull;
+  HIPCHK(hipHostMalloc((void**)&c->h_feedback, 2 * sizeof(StepFeedback), hipHostMallocDefault));
+  for (int k = 0; k < 2; ++k) c->h_feedback[k] = kNoFeedback;
   for (int k = 0; k < 2; ++k) HIPCHK(hipEventCreateWithFlags(&c->iev[k], hipEventDisableTiming));
   HIPCHK(hipMalloc(&c->d_prof, sizeof(unsigned long long) * LQRO_PROF_WORDS));
   HIPCHK(hipMemset(c->d_prof, 0, sizeof(unsigned long long) * LQRO_PROF_WORDS));
@@ -624,8 +592,8 @@ static int ctx_alloc(lqro_ctx* c) {
     HIPCHK(hipMalloc(&c->d_qstale, sizeof(int) * (slots ? slots : 1)));
     HIPCHK(hipMalloc(&c->d_hbuild, sizeof(unsigned long long) * 4 * LQRO_HBUILD_CAP));
     HIPCHK(hipMalloc(&c->d_prevq, sizeof(int) * (size_t)c->hot_cap));
-    HIPCHK(hipMalloc(&c->d_hot2, sizeof(int) * 8));
-    HIPCHK(hipMemset(c->d_hot2, 0, sizeof(int) * 8));
+    HIPCHK(hipMalloc(&c->d_hot2, sizeof(int) * LQRO_H2_WORDS));
+    HIPCHK(hipMemset(c->d_hot2, 0, sizeof(int) * LQRO_H2_WORDS));
     HIPCHK(hipMemset(c->d_prevq, 0xFF, sizeof(int) * (size_t)c->hot_cap));
     HIPCHK(hipMemset(c->d_qstale, 0xFF, sizeof(int) * (slots ? slots : 1)));
     HIPCHK(hipMemset(c->d_hbuild, 0, sizeof(unsigned long long) * 4 * LQRO_HBUILD_CAP));
@@ -655,65 +623,7 @@ int lqro_create(const lqro_config* cfg, lqro_ctx** out) {
   c->cfg = g;
   c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   c->qhull_order = (g.flags & LQRO_FLAG_QHULL_ORDER) ? 1 : 0;
-  {
-    const char* qb = getenv("LQRO_QHULL_BIG");
-    c->qhull_big = qb ? atoi(qb) != 0 : 0;
-  }
-  {
-    // CUs running k_hull workers beside k_pair (the hot-pair hulls); default 3/8
-    const char* e = getenv("LQRO_SIDE_HULL_CUS");
-    c->side_cus = e ? atoi(e) : (3 * c->n_cu) / 8;
-    if (c->side_cus < 0) c->side_cus = 0;
-    if (c->side_cus > c->n_cu / 2) c->side_cus = c->n_cu / 2;
-    const char* hb = getenv("LQRO_HULL_BIG");   // every hull job in k_hull_big (A/B runs)
-    c->hull_big_only = hb ? atoi(hb) != 0 : 0;
-    const char* lh = getenv("LQRO_LOCAL_HULL");
-    c->local_hull = lh ? atoi(lh) != 0 : 1;
-    const char* ls = getenv("LQRO_LOCAL_SIDE_CUS");
-    c->lside_cus = ls ? atoi(ls) : (3 * c->n_cu) / 16;
-    if (c->lside_cus < 0) c->lside_cus = 0;
-    if (c->lside_cus > c->n_cu / 2) c->lside_cus = c->n_cu / 2;
-    const char* h = getenv("LQRO_HOT");
-    c->hot_on = h ? atoi(h) != 0 : 1;
-    const char* ht = getenv("LQRO_HOT_T");
-    const char* hr = getenv("LQRO_HOT_R");
-    c->hot_t = ht ? atof(ht) : 3.0;
-    c->hot_r = hr ? atof(hr) : 3.0;
-    const char* lp = getenv("LQRO_LHULL_PROFILE");
-    c->lhull_prof = lp ? atoi(lp) != 0 : 0;
-    const char* hm = getenv("LQRO_HOT_MAX_INSIDE");
-    c->hot_max_inside = hm ? atol(hm) : -1L;
-    const char* el = getenv("LQRO_EARLY_LP");
-    c->early_lp = el ? atoi(el) != 0 : 1;
-    // Qhull order: the last step's inside-hull pairs in a hot launch of their
-    // own on the side stream, so the builds start when they are found rather
-    // than behind the other hot pairs' stragglers (which go to the main stream)
-    const char* hs = getenv("LQRO_HOT_SPLIT");
-    c->hot_split = hs ? atoi(hs) != 0 : 1;
-    const char* hp = getenv("LQRO_HOT_SPEC");
-    c->hot_spec = hp ? atoi(hp) != 0 : 1;
-    const char* qsp = getenv("LQRO_QHULL_SPARE");
-    c->qspare = qsp ? atoi(qsp) : 4;
-    const char* qpc = getenv("LQRO_QHULL_SIDE_PCT");
-    c->qside_pct = qpc ? std::max(1, std::min(100, atoi(qpc))) : 100;
-    // off by default: with 3 waves a CU the side workers sweep rows at ~1/5 of a
-    // 16-wave workgroup's rate, so where the sweep outlasts the builds (C4:
-    // 227 vs 114 ms per step) it loses; at C3 it ties (22.0 ms either way)
-    const char* qs = getenv("LQRO_QSIDE");
-    c->qside = qs ? atoi(qs) != 0 : 0;
-    // a build past k_qhull's caps rebuilt at once on its CU (q3_big_inline)
-    // instead of in the k_qhull_big launch after the sweep
-    const char* qi = getenv("LQRO_QHULL_INLINE_BIG");
-    c->qhull_inline = qi ? atoi(qi) != 0 : 1;
-    const char* qf = getenv("LQRO_QHULL_FLAGS");
-    c->qhull_flags = qf ? atoi(qf) : 23;
-    // the side's width from the measured work of the step two before (the
-    // sweep's CU time, the builds' total and longest): no wider than leaves
-    // the sweep no longer than the builds (LQRO_QHULL_BALANCE=0: one CU per
-    // expected build, round 5's rule)
-    const char* qbal = getenv("LQRO_QHULL_BALANCE");
-    c->qbalance = qbal ? atoi(qbal) != 0 : 1;
-  }
+  c->knobs = knobs_from_env(c->n_cu);
   c->rb = g.row_begin;
   c->re = (g.row_end > g.row_begin) ? g.row_end : g.n_agents;
   if (g.row_end == 0 && g.row_begin == 0) { c->rb = 0; c->re = g.n_agents; }
@@ -843,7 +753,6 @@ int lqro_set_gains(lqro_ctx* c, const double* A, const double* B, const double* 
 
 static int enqueue_tail(lqro_ctx* c, const double* d_x, const double* d_vgoal, double* d_newv, hipStream_t s,
                         const double* d_rowtab);
-static int qhull_side_balance(int n, double w_sweep, double w_build, double b_max);
 
 // the LP launch's arguments for this context's rows (every row, the tail's
 // k_lp4 list)
@@ -852,23 +761,32 @@ static LpArgs lp_args(const lqro_ctx* c, int npr, const double* d_vgoal, double*
   La.npr = npr; La.nrows = c->nrows; La.row_begin = c->rb; La.row_stride = c->rs; La.vmax = c->cfg.vmax_lp;
   La.slots = c->d_planes; La.compact = c->d_lpcompact; La.proj = c->d_lpscratch;
   La.vgoal = d_vgoal; La.newv = d_newv; La.prof = c->d_prof;
-  La.lp4_list = c->d_lp4; La.lp4_count = c->d_hcount + 9; La.lp4_next = c->d_hcount + 10;
+  La.lp4_list = c->d_lp4; La.lp4_count = c->d_hcount + LQRO_HC_LP4; La.lp4_next = c->d_hcount + LQRO_HC_LP4_NEXT;
   return La;
 }
 
-// phase 0: the whole step.  Row shards in Qhull order split it around the
-// exchange of the loop-carried normal (lqro_step_device_begin / _end):
-// phase 1 runs the sweep and the hulls and writes each own row's last
-// normal into d_rowtab; phase 2 (enqueue_tail) resolves the facet-0 pairs
-// against every rank's rows and runs the LP.
-static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, double* d_newv,
-                        hipStream_t s, int phase = 0, double* d_rowtab = nullptr) {
+// what the planner reads of the context and of the kernels' headers
+// (d_lpnv: where an early LP would write, d_newv: the caller's buffer)
+static StepShape step_shape(const lqro_ctx* c, int phase, const double* d_lpnv, const double* d_newv) {
+  StepShape S{};
+  S.n_cu = c->n_cu; S.nrows = c->nrows; S.npr = c->npr; S.nbr_k = c->nbr_k;
+  S.hnp = (size_t)c->cfg.horizon * c->cfg.n_points;
+  S.per_agent = c->per_agent; S.qhull_order = c->qhull_order; S.phase = phase;
+  S.has_newv = d_lpnv != nullptr; S.newv_is_callers = d_lpnv == d_newv;
+  S.waves = c->pa.waves; S.lds_wave = c->pa.lds_wave; S.wave_doubles = c->pa.wave_doubles;
+  S.hull_lds_max_hnp = kHullLdsMaxHNP; S.hull_lds_doubles = sizeof(HullMemC) / 8; S.hull_cwaves = HULL_CWAVES;
+  S.qhull_lds_doubles = qhull_lds_doubles(); S.lp_lds_max = kLpLdsMax;
+  S.early_lp_max_npr = LQRO_EARLY_LP_MAX_NPR; S.row_big = LQRO_ROW_BIG;
+  return S;
+}
+
+// k_pair's arguments for the row launch; the hot launches derive theirs
+// (hot_main, hot_side)
+static PairArgs pair_args(const lqro_ctx* c, const StepPlan& plan, const double* d_x) {
   const lqro_config& g = c->cfg;
   PairArgs P = c->pa;
   P.N = g.n_agents; P.H = g.horizon; P.NP = g.n_points; P.min_reach = g.min_reach;
-  // culling on: each row's slots are its K neighbours (k_nbr), not its N-1 pairs
-  const int npr = c->nbr_k > 0 ? std::min(c->nbr_k, c->npr) : c->npr;
-  P.row_begin = c->rb; P.row_stride = c->rs; P.nrows = c->nrows; P.npr = npr;
+  P.row_begin = c->rb; P.row_stride = c->rs; P.nrows = c->nrows; P.npr = plan.npr;
   P.per_agent = c->per_agent;
   P.vmax = g.vmax_reach;
   P.r2 = g.vmax_reach * g.vmax_reach;
@@ -877,194 +795,73 @@ static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   P.T = c->d_T; P.NCF = c->d_NCF; P.R = c->d_R; P.TF = c->d_TF; P.S = c->d_S;
   P.shash = c->d_shash; P.x = d_x;
   P.planes = c->d_planes; P.recs = c->d_recs;
-  P.hull_queue = c->d_hq; P.hull_count = c->d_hcount; P.hull_cap = c->hull_cap;
+  P.hull_queue = c->d_hq; P.hull_count = c->d_hcount + LQRO_HC_HULL; P.hull_cap = c->hull_cap;
   P.stats = c->d_stats;
-  P.prof = c->d_prof + 32 + 2 * 4096;
-  // persistent: one workgroup per CU (LDS-bound), rows off a queue.
-  //   main:  k_prio -> k_pair(rows, n_cu - side blocks) -> [side done] -> k_hull -> k_hull_big -> k_lp
-  //   side:  [k_prio done] -> k_pair(hot, side blocks) -> k_side(hot hulls, then rows)
-  // The hot launch computes the pairs k_prio predicts to be inside-hull, so
-  // their hulls run on the side CUs while the row launch sweeps the rest on
-  // the others; each side workgroup joins the sweep as soon as the hull
-  // queue is drained.  No kernel waits on another running kernel (streams
-  // sharing a hardware queue just serialise), and the two concurrent grids
-  // add up to one workgroup per CU.  Hull jobs the prediction missed are
-  // taken by the k_hull after the sweep.
-  P.row_counter = c->d_hcount + 4;
+  P.prof = c->d_prof + LQRO_PROF_PAIR;
+  P.row_counter = c->d_hcount + LQRO_HC_ROW;
+  P.row_split = plan.row_split;
   P.qnrm = c->qhull_order ? c->d_qnrm : nullptr;
-  // the context's scratch (queues, counters, plane slots, tables) is reused by
-  // every step: a step enqueued on another stream than the last one, or a
-  // set_gains on c->stream, must not overlap the step still in flight
-  if (c->stepped) HIPCHK(hipStreamWaitEvent(s, c->ev[3], 0));
-  HIPCHK(hipEventRecord(c->ev[0], s));
-  HIPCHK(hipMemsetAsync(c->d_hcount, 0, sizeof(int) * 16, s));
-  HIPCHK(hipMemsetAsync(c->d_stats, 0, sizeof(unsigned long long) * LQRO_ST_WORDS, s));
-  HIPCHK(hipMemsetAsync(c->d_hq, 0xFF, sizeof(int) * (size_t)c->hull_cap, s));
-  // Qhull order: the normal the last step's last eligible pair left enters this step
-  if (c->qhull_order)
-    HIPCHK(hipMemcpyAsync(c->d_carry, c->d_carry + 3, sizeof(double) * 3, hipMemcpyDeviceToDevice, s));
-  P.nbr_list = nullptr;
-  if (c->nbr_k > 0) {
-    hipLaunchKernelGGL(k_nbr, dim3((unsigned)c->nrows), dim3(64), 0, s, d_x, g.x_dim, g.n_agents, c->rb, c->rs,
-                       c->npr,
-                       c->nbr_r2, c->nbr_k, npr, c->d_nbrlist, c->d_stats);
-    HIPCHK(hipGetLastError());
-    P.nbr_list = c->d_nbrlist;
-  }
-  // the LDS hull variant packs outside-set extents in 32 bits (lqro_hull.hpp
-  // seg_put: 15-bit count, 17-bit offset / 4 into HULL_SBMULT * H*NP entries)
-  const bool lds_ok = (size_t)g.horizon * g.n_points <= kHullLdsMaxHNP && !c->hull_big_only;
-  const long slots = (long)c->nrows * npr;
-  // k_side sweeps rows in the hull's LDS (HullMemC) after its hulls: as many
-  // of its waves take pairs as per-wave regions fit beside the row tables
-  const long side_room = (long)(sizeof(HullMemC) / 8) - P.lds_wave;
-  const int side_waves = side_room > 0 ? (int)std::min<long>(std::min(HULL_CWAVES, P.waves),
-                                                              side_room / P.wave_doubles) : 0;
-  // the overlap pays where the hot pairs' hulls fit k_side's LDS topology
-  // (C3: 177 hulls of <= 1,700 vertices); at H*NP > 16,383 (C5: 40 % of the
-  // hulls outgrow its 2,048 vertices and retry in k_hull_big) the plain
-  // schedule is faster (516 vs 1,150 ms per C5 shard step, scripts/c5_once.py)
-  // crowded swarms (many inside-hull pairs in an earlier step: the value is
-  // read without waiting for the copy, it only picks the schedule, and every
-  // schedule gives bit-identical results) take the plain schedule
-  // The inside-hull count that picks the schedule is step t-2's, read after
-  // that step's copy completed (the host runs at most one step ahead of the
-  // GPU here), so the schedule does not depend on host/GPU timing.
-  const int slot = (int)(c->nstep & 1);
-  unsigned long long inside_prev = ~0ull;
-  double w_sweep = 0.0, w_build = 0.0, b_max = 0.0;   // CU-ms, ms (the step two before)
-  unsigned long long retried_prev = 0;
-  if (c->nstep >= 2) {
-    HIPCHK(hipEventSynchronize(c->iev[slot]));
-    inside_prev = c->h_inside[8 * slot];
-    w_sweep = 1e-5 * (double)c->h_inside[8 * slot + 1];
-    w_build = 1e-5 * (double)c->h_inside[8 * slot + 2];
-    b_max = 1e-5 * (double)c->h_inside[8 * slot + 3];
-    retried_prev = c->h_inside[8 * slot + 4];
-  }
-  const bool known = inside_prev != ~0ull;
-  const bool lhull = c->local_hull || c->qhull_order;   // k_lhull or k_qhull on the side
-  int side = lhull ? c->lside_cus : c->side_cus;
-  const unsigned long long qspare =
-      !known ? 0ull : c->qspare >= 0 ? (unsigned long long)c->qspare : inside_prev / 16 + 4;
-  // the side's builds (workers): the last step's inside-hull count, or a
-  // share of it (LQRO_QHULL_SIDE_PCT: the longest builds first, k_prio_save)
-  unsigned long long qwant =
-      known ? (inside_prev * (unsigned long long)c->qside_pct + 99ull) / 100ull + qspare : 0ull;
-  if (c->qhull_order && c->qbalance && known && w_sweep > 0.0 && b_max > 0.0)
-    qwant = std::min(qwant, (unsigned long long)qhull_side_balance(c->n_cu, w_sweep, w_build, b_max));
-  if (c->qhull_order) {
-    // Qhull's build is one long dependent chain per pair (one wave per CU):
-    // the side takes one CU per expected hull, so every hot hull starts at
-    // once, plus a few for pairs new this step (LQRO_QHULL_SPARE, default 4:
-    // a pair beyond them waits for the first build to end), leaving at least
-    // an eighth of the CUs to the sweep (unknown count: half the CUs).  With
-    // speculative builds the main stream's sweep is as long as the slowest
-    // build: each CU given back to it shortens the step (C3: 192 -> 181 side
-    // CUs, 19.85 -> 19.35 ms, profiles/r5ak_ab_qhull_spare.txt)
-    const unsigned long long want = known ? qwant : (unsigned long long)(c->n_cu / 2);
-    side = (int)std::min<unsigned long long>((unsigned long long)(c->n_cu - c->n_cu / 8),
-                                             std::max<unsigned long long>((unsigned long long)side, want));
-  } else if (lhull) {
-    // local hulls: at most ~3.7 inside-hull pairs per side CU (C3: 177 on
-    // 48 CUs), widening up to half the CUs as the swarm gets denser
-    if (known)
-      side = (int)std::max<unsigned long long>(
-          (unsigned long long)side,
-          std::min<unsigned long long>(c->n_cu / 2, (inside_prev * 10ull + 36ull) / 37ull));
-  } else if (known && inside_prev > 2ull * (unsigned long long)side) {
-    side = std::min(c->n_cu / 2, (4 * side) / 3);
-  }
-  // local hulls: the overlap pays up to ~16 inside-hull pairs per CU of the
-  // widest side (1,067 at 22 m: 15.5 vs 18.0 ms plain; 2,496 at 16 m: a tie)
-  // (Qhull's order: the overlap always pays, the hulls outlast the sweep)
-  const long max_inside = c->hot_max_inside >= 0 ? c->hot_max_inside
-                          : c->qhull_order   ? LONG_MAX
-                          : (lhull ? 16L * std::max(side, c->n_cu / 2) : 4L * side);
-  const bool crowded = known && inside_prev > (unsigned long long)max_inside;
-  // with the local hull the side stream is k_pair(hot) -> k_lhull -> k_pair
-  // (rows, the same row queue): no LDS-topology condition
-  // (Qhull order: until the work of a step is known — a context's first two
-  // steps — the plain schedule: every CU sweeps, then the builds.  A side
-  // guessed at half the CUs starved the sweep where it outweighs the builds:
-  // C5's whole swarm took 11.7 s per unknown step against 3.4 s plain)
-  const bool hot = c->hot_on && c->n_cu >= 64 && slots >= 65536 && c->nbr_k <= 0 && !crowded && side >= 1 &&
-                   (known || !c->qhull_order) &&
-                   (lhull || (lds_ok && (size_t)g.horizon * g.n_points <= 16383 && side_waves >= 1));
-  const int nwait = hot ? side : 0;
-  P.row_split = std::max(1, std::min(16, (2 * c->n_cu + c->nrows - 1) / c->nrows));
-  // Qhull order: the side's k_qhull workers sweep rows in their build's LDS
-  // once the hot builds are taken (k_qside, 3 waves a CU): rows in units of
-  // ~128 pairs, so a 3-wave worker's last unit ends soon after the 16-wave
-  // workgroups' (shared gains: the tables are staged once per workgroup)
-  const long qside_room = (long)qhull_lds_doubles() - P.lds_wave;
-  const int qside_waves = qside_room > 0 ? (int)std::min<long>(3, qside_room / P.wave_doubles) : 0;
-  const bool qside = hot && c->qside && c->qhull_order && !c->qhull_big && qside_waves >= 1;
-  if (qside && !c->per_agent) P.row_split = std::max(P.row_split, std::min(16, std::max(1, npr / 128)));
-  // early LP (Qhull order, beside the hulls): a row whose planes are all
-  // final runs its LP at once — in a k_lp_lds after the main sweep, or in the
-  // k_qhull job that completes it (lqro_hull.hpp hull_row_done; rows of at
-  // most LQRO_EARLY_LP_MAX_NPR pairs, longer ones go to the tail) — and the
-  // tail only runs the rest (rows waiting on k_stale, rows closed late)
-  // (the split step, lqro_step_device_begin / _end: the early rows' newV go
-  // to the context's own buffer, copied into the caller's by _end; rows with
-  // a facet-0 pair wait for the row-normal exchange in the tail as before)
-  double* d_lpnv = d_newv != nullptr ? d_newv : (phase == 1 ? c->d_newv : nullptr);
-  const bool early = hot && c->early_lp && c->qhull_order && !c->qhull_big && phase != 2 && c->nbr_k <= 0 &&
-                     (size_t)npr * 32 <= kLpLdsMax && d_lpnv != nullptr;
-  c->early_step = early ? 1 : 0;
-  c->early_internal = early && d_lpnv != d_newv ? 1 : 0;
-  P.rowpend = early ? c->d_rowpend : nullptr;
-  if (early) HIPCHK(hipMemsetAsync(c->d_rowpend, 0, sizeof(int) * 2 * (size_t)c->nrows, s));
-  const int units = c->nrows * P.row_split;
-  const unsigned nblk = (unsigned)std::min(units, c->n_cu - nwait);
-  const unsigned nside = (unsigned)std::max(0, std::min(units - (int)nblk, nwait));
+  P.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;   // (k_nbr fills it)
+  P.rowpend = plan.early ? c->d_rowpend : nullptr;
   P.hot_list = nullptr; P.hot_mark = nullptr; P.hot_count = nullptr;
   P.hot_next = nullptr; P.hot_cap = 0; P.hot_only = 0; P.hot_done = nullptr;
-  // Qhull order, split hot launch (every pair of the last step's list gets a
-  // side CU of its own): side: the last step's inside-hull pairs, then
-  // k_qhull; main: k_prio's other hot pairs, then the rows.  k_qhull's workers
-  // wait for the main hot launch before leaving an empty queue.
-  const bool split = hot && c->qhull_order && c->hot_split && !qside && !c->qhull_big && known &&
-                     qwant <= (unsigned long long)nwait;
-  // speculative builds (with the split): the last step's inside-hull pairs go
-  // straight into the hull queue, so the side's k_qhull workers start building
-  // them at once instead of after their evaluation (~0.5 ms at C3); the main
-  // stream's hot launch evaluates them first, and each build commits only if
-  // its pair is inside (PairArgs::spec_mark)
-  const bool spec = split && c->hot_spec;
-  if (hot) {
-    PrioArgs Q{};
-    Q.npr = c->npr; Q.nrows = c->nrows; Q.row_begin = c->rb; Q.row_stride = c->rs; Q.X = g.x_dim; Q.x = d_x;
-    Q.t_hot = c->hot_t; Q.r2_hot = c->hot_r * c->hot_r;   // seconds, metres (scheduling heuristic)
-    Q.list = c->d_hotlist; Q.mark = c->d_hotmark; Q.count = c->d_hcount + 6; Q.cap = c->hot_cap;
-    Q.rowpend = P.rowpend;
-    if (split) {
-      HIPCHK(hipMemsetAsync(c->d_hot2 + 1, 0, sizeof(int) * 6, s));
-      Q.prev = c->d_prevq; Q.prevn = c->d_hot2; Q.hot1n = c->d_hot2 + 1; Q.hot2next = c->d_hot2 + 3;
-      if (spec) { Q.hq = c->d_hq; Q.hcount = c->d_hcount; Q.hq_cap = c->hull_cap; Q.spec_n = c->d_hot2 + 5; }
-      hipLaunchKernelGGL(k_prio_prev, dim3(1), dim3(256), 0, s, Q);
-      HIPCHK(hipGetLastError());
-    }
-    const long nb = std::min<long>((slots + 255) / 256, 8L * c->n_cu);
-    hipLaunchKernelGGL(k_prio, dim3((unsigned)nb), dim3(256), 0, s, Q);
-    HIPCHK(hipGetLastError());
-    P.hot_list = c->d_hotlist; P.hot_mark = c->d_hotmark; P.hot_count = c->d_hcount + 6;
-    P.hot_next = c->d_hcount + 7; P.hot_cap = c->hot_cap;
+  if (plan.hot) {
+    P.hot_list = c->d_hotlist; P.hot_mark = c->d_hotmark; P.hot_count = c->d_hcount + LQRO_HC_HOT;
+    P.hot_next = c->d_hcount + LQRO_HC_HOT_NEXT; P.hot_cap = c->hot_cap;
   }
+  return P;
+}
+
+// the split's hot launch on the main stream: k_prio's pairs after the last step's
+static PairArgs hot_main(const lqro_ctx* c, const StepPlan& plan, PairArgs P) {
+  P.hot_only = 1;
+  P.hot_next = c->d_hot2 + LQRO_H2_HOT2_NEXT;
+  P.hot_done = c->d_hot2 + LQRO_H2_HOT2_DONE;
+  if (plan.spec) P.spec_mark = c->d_hotmark;   // (its list from position 0: the speculative pairs first)
+  return P;
+}
+
+// the side stream's hot launch: the whole hot list, or with the split the
+// last step's inside-hull pairs
+static PairArgs hot_side(const lqro_ctx* c, const StepPlan& plan, PairArgs P) {
+  P.hot_only = 1;
+  if (plan.split) { P.hot_count = c->d_hot2 + LQRO_H2_HOT1; P.hot_next = c->d_hot2 + LQRO_H2_HOT1_NEXT; }
+  return P;
+}
+
+static PrioArgs prio_args(const lqro_ctx* c, const StepPlan& plan, const PairArgs& P) {
+  PrioArgs Q{};
+  Q.npr = c->npr; Q.nrows = c->nrows; Q.row_begin = c->rb; Q.row_stride = c->rs; Q.X = c->cfg.x_dim; Q.x = P.x;
+  Q.t_hot = c->knobs.hot_t; Q.r2_hot = c->knobs.hot_r * c->knobs.hot_r;   // seconds, metres (scheduling heuristic)
+  Q.list = c->d_hotlist; Q.mark = c->d_hotmark; Q.count = c->d_hcount + LQRO_HC_HOT; Q.cap = c->hot_cap;
+  Q.rowpend = P.rowpend;
+  if (plan.split) {
+    Q.prev = c->d_prevq; Q.prevn = c->d_hot2 + LQRO_H2_PREV; Q.hot1n = c->d_hot2 + LQRO_H2_HOT1;
+    Q.hot2next = c->d_hot2 + LQRO_H2_HOT2_NEXT;
+    if (plan.spec) { Q.hq = c->d_hq; Q.hcount = c->d_hcount; Q.hq_cap = c->hull_cap; Q.spec_n = c->d_hot2 + LQRO_H2_SPEC; }
+  }
+  return Q;
+}
+
+// the hull kernels' arguments (every family reads the same struct): the main
+// queue, block 0's scratch; the variants below derive from it
+static HullArgs hull_args(const lqro_ctx* c, const StepPlan& plan, const PairArgs& P, const double* d_vgoal,
+                          double* d_lpnv) {
+  const lqro_config& g = c->cfg;
   HullArgs Hh{};
   Hh.N = g.n_agents; Hh.X = g.x_dim; Hh.H = g.horizon; Hh.NP = g.n_points;
-  Hh.row_begin = c->rb; Hh.row_stride = c->rs; Hh.npr = npr; Hh.per_agent = c->per_agent;
+  Hh.row_begin = c->rb; Hh.row_stride = c->rs; Hh.npr = plan.npr; Hh.per_agent = c->per_agent;
   Hh.nbr_list = P.nbr_list;
   Hh.r2 = P.r2; Hh.r2_lo = P.r2_lo; Hh.r2_hi = P.r2_hi;
-  Hh.T = c->d_T; Hh.NCF = c->d_NCF; Hh.S = c->d_S; Hh.x = d_x;
+  Hh.T = c->d_T; Hh.NCF = c->d_NCF; Hh.S = c->d_S; Hh.x = P.x;
   Hh.planes = c->d_planes; Hh.recs = c->d_recs;
-  Hh.queue = c->d_hq; Hh.count = c->d_hcount; Hh.cap = c->hull_cap; Hh.next = c->d_hnext;
+  Hh.queue = c->d_hq; Hh.count = c->d_hcount + LQRO_HC_HULL; Hh.cap = c->hull_cap;
+  Hh.next = c->d_hcount + LQRO_HC_HULL_NEXT;
   Hh.scratch = c->d_hscratch; Hh.iscratch = c->d_hiscratch; Hh.fscratch = c->d_hfscratch;
   Hh.sb = reinterpret_cast<HullPt*>(c->d_hfaces);
   Hh.fbest = c->d_hfbest;
   Hh.vpid = c->d_hvpid; Hh.stack = c->d_hstack;
-  Hh.rqueue = c->d_rq; Hh.rcount = c->d_hcount + 2; Hh.rnext = c->d_hcount + 3;
+  Hh.rqueue = c->d_rq; Hh.rcount = c->d_hcount + LQRO_HC_RETRY; Hh.rnext = c->d_hcount + LQRO_HC_RETRY_NEXT;
   Hh.bigmem = c->d_hbig;
   Hh.wide = c->d_hwide;
   Hh.bag = c->d_hbag;
@@ -1072,159 +869,256 @@ static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   Hh.prof = c->d_prof;
   Hh.block_base = 0;
   Hh.big_main = 0;
-  Hh.lqueue = c->d_lq; Hh.lcount = c->d_hcount + 11; Hh.ldone = c->d_hcount + 13;
-  Hh.lfail = c->d_prof + 32 + 2 * 4096 + 32;
+  Hh.lqueue = c->d_lq; Hh.lcount = c->d_hcount + LQRO_HC_LHAND; Hh.ldone = c->d_hcount + LQRO_HC_LDONE;
+  Hh.lfail = c->d_prof + LQRO_PROF_LFAIL;
   Hh.ext_pts = nullptr; Hh.ext_n = 0; Hh.ext_max = 0; Hh.ext_facets = nullptr; Hh.ext_nf = nullptr;
   Hh.ext_full = 0;
   // per-job stamps only when asked for (LQRO_LHULL_PROFILE=1, scripts/lhull_jobs.py);
   // lfail counts hand-over reasons since the context was created
-  Hh.ljobs = c->lhull_prof ? c->d_prof + 32 + 2 * 4096 + 48 : nullptr;
+  Hh.ljobs = c->knobs.lhull_prof ? c->d_prof + LQRO_PROF_LJOBS : nullptr;
   Hh.qscratch = c->d_qscratch; Hh.qstride = c->qstride; Hh.qnrm = c->d_qnrm;
-  Hh.qstale = c->d_qstale; Hh.qstale_count = c->d_hcount + 15; Hh.qstale_cap = c->hull_cap;
-  Hh.rowpend = P.rowpend; Hh.rowclaim = early ? c->d_rowclaim : nullptr;
-  Hh.row_lp = npr <= LQRO_EARLY_LP_MAX_NPR ? 1 : 0;
-  Hh.row_target = P.row_split * LQRO_ROW_BIG;
+  Hh.qstale = c->d_qstale; Hh.qstale_count = c->d_hcount + LQRO_HC_FACET0; Hh.qstale_cap = c->hull_cap;
+  Hh.rowpend = P.rowpend; Hh.rowclaim = plan.early ? c->d_rowclaim : nullptr;
+  Hh.row_lp = plan.row_lp;
+  Hh.row_target = plan.row_target;
   Hh.lp_vgoal = d_vgoal; Hh.lp_newv = d_lpnv; Hh.lp_vmax = g.vmax_lp;
   Hh.hbuild = c->d_hbuild; Hh.hbuild_cap = LQRO_HBUILD_CAP;
-  // (k_qhull's in-place rebuild of capped builds where they happen: hulls of
-  // more than 10,000 points (C5's ~19,000), or builds capped two steps before)
-  Hh.big_inline =
-      c->qhull_inline && !c->qhull_big && ((size_t)g.horizon * g.n_points > 10000 || retried_prev > 0) ? 1 : 0;
-  Hh.qflags = c->qhull_flags;
-  if (g.x_dim != 16 && g.x_dim != 12) return LQRO_E_ARG;
-  // the row launch is submitted before the side stream's work: should the two
-  // streams land on one hardware queue (a second context in the process), the
-  // main grid still runs first on its CUs instead of k_side's row tail
-  // sweeping every row on the side CUs alone
-  if (nwait > 0) HIPCHK(hipEventRecord(c->xev[0], s));
-  if (split) {   // the main stream's hot launch: k_prio's pairs after the last step's
-    PairArgs P2 = P;
-    P2.hot_only = 1;
-    P2.hot_next = c->d_hot2 + 3;
-    P2.hot_done = c->d_hot2 + 4;
-    if (spec) P2.spec_mark = c->d_hotmark;   // (its list from position 0: the speculative pairs first)
-    launch_pair(g.x_dim, dim3(nblk), dim3(P.waves * 64), c->lds_bytes, s, P2);
+  Hh.big_inline = plan.big_inline;
+  Hh.qflags = c->knobs.qhull_flags;
+  return Hh;
+}
+
+// speculative builds: the marks, and the ticket over the jobs k_prio_prev queued
+static HullArgs with_spec(const lqro_ctx* c, HullArgs H) {
+  H.spec_mark = c->d_hotmark; H.spec_n = c->d_hot2 + LQRO_H2_SPEC; H.spec_next = c->d_hot2 + LQRO_H2_SPEC_NEXT;
+  return H;
+}
+
+// the full hull on the pairs k_lhull handed over instead of the main queue
+static HullArgs handed_over(const lqro_ctx* c, HullArgs H) {
+  H.queue = c->d_lq; H.count = c->d_hcount + LQRO_HC_LHAND; H.next = c->d_hcount + LQRO_HC_LHAND_NEXT;
+  return H;
+}
+
+// The step's first launches on the caller's stream: behind the last step, the
+// counters and queues reset, the neighbour lists, the hot list.
+static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, hipStream_t s) {
+  const lqro_config& g = c->cfg;
+  // the context's scratch (queues, counters, plane slots, tables) is reused by
+  // every step: a step enqueued on another stream than the last one, or a
+  // set_gains on c->stream, must not overlap the step still in flight
+  if (c->stepped) HIPCHK(hipStreamWaitEvent(s, c->ev[3], 0));
+  HIPCHK(hipEventRecord(c->ev[0], s));
+  HIPCHK(hipMemsetAsync(c->d_hcount, 0, sizeof(int) * LQRO_HC_WORDS, s));
+  HIPCHK(hipMemsetAsync(c->d_stats, 0, sizeof(unsigned long long) * LQRO_ST_WORDS, s));
+  HIPCHK(hipMemsetAsync(c->d_hq, 0xFF, sizeof(int) * (size_t)c->hull_cap, s));
+  // Qhull order: the normal the last step's last eligible pair left enters this step
+  if (c->qhull_order)
+    HIPCHK(hipMemcpyAsync(c->d_carry, c->d_carry + 3, sizeof(double) * 3, hipMemcpyDeviceToDevice, s));
+  if (c->nbr_k > 0) {
+    hipLaunchKernelGGL(k_nbr, dim3((unsigned)c->nrows), dim3(64), 0, s, P.x, g.x_dim, g.n_agents, c->rb, c->rs,
+                       c->npr,
+                       c->nbr_r2, c->nbr_k, plan.npr, c->d_nbrlist, c->d_stats);
     HIPCHK(hipGetLastError());
   }
-  launch_pair(g.x_dim, dim3(nblk), dim3(P.waves * 64), c->lds_bytes, s, P);
-  HIPCHK(hipGetLastError());
-  if (early) {
-    // the rows the main sweep closed (no open hull): their LP on its CUs
-    // while the side stream's hulls run
-    LpArgs Le = lp_args(c, npr, d_vgoal, d_lpnv);
-    Le.lp4_list = nullptr;
-    Le.rowpend = c->d_rowpend; Le.rowclaim = c->d_rowclaim; Le.row_target = Hh.row_target; Le.mode = 1;
-    HIPCHK(hipFuncSetAttribute((const void*)k_lp_lds<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLpLdsMax));
-    hipLaunchKernelGGL(k_lp_lds<8>, dim3((unsigned)c->nrows), dim3(64), (size_t)npr * 32, s, Le);
-    HIPCHK(hipGetLastError());
-  }
-  if (nwait > 0) {
-    HIPCHK(hipStreamWaitEvent(c->side, c->xev[0], 0));
-    PairArgs Ph = P;
-    Ph.hot_only = 1;
-    if (split) { Ph.hot_count = c->d_hot2 + 1; Ph.hot_next = c->d_hot2 + 2; }
-    if (!spec) {   // (speculative builds: the side goes straight to k_qhull)
-      launch_pair(g.x_dim, dim3(nwait), dim3(P.waves * 64), c->lds_bytes, c->side, Ph);
+  if (plan.early) HIPCHK(hipMemsetAsync(c->d_rowpend, 0, sizeof(int) * 2 * (size_t)c->nrows, s));
+  if (plan.hot) {
+    const PrioArgs Q = prio_args(c, plan, P);
+    if (plan.split) {
+      HIPCHK(hipMemsetAsync(c->d_hot2 + LQRO_H2_HOT1, 0, sizeof(int) * (LQRO_H2_SPEC_NEXT - LQRO_H2_HOT1 + 1), s));
+      hipLaunchKernelGGL(k_prio_prev, dim3(1), dim3(256), 0, s, Q);
       HIPCHK(hipGetLastError());
     }
-    if (c->qhull_order) {
-      // the hot pairs' hulls in Qhull's order (k_qhull leaves when the queue
-      // is empty), then the row sweep
-      if (qside) {
-        PairArgs Pq = P;
-        Pq.max_waves = qside_waves;
-        if (nside == 0) Pq.nrows = 0;
-        launch_qside(g.x_dim, dim3(std::min(nwait, c->qworkers)), c->side, Hh, Pq);
-        HIPCHK(hipGetLastError());
-      } else {
-        if (!c->qhull_big) {
-          HullArgs Hs = Hh;
-          if (split) { Hs.prod_done = c->d_hot2 + 4; Hs.prod_total = (int)nblk; }
-          if (spec) { Hs.spec_mark = c->d_hotmark; Hs.spec_n = c->d_hot2 + 5; Hs.spec_next = c->d_hot2 + 6; }
-          launch_qhull(dim3(std::min(nwait, c->qworkers)), c->side, Hs);
-          HIPCHK(hipGetLastError());
-        }
-        if (nside > 0) {
-          launch_pair(g.x_dim, dim3(nwait), dim3(P.waves * 64), c->lds_bytes, c->side, P);
-          HIPCHK(hipGetLastError());
-        }
-      }
-    } else if (c->local_hull) {
-      // the hot pairs' local hulls (k_lhull leaves when the queue is empty:
-      // later jobs go to the k_lhull after the sweep), then the row sweep
-      launch_lhull(dim3(nwait), c->side, Hh);
+    const long nb = std::min<long>((plan.slots + 255) / 256, 8L * c->n_cu);
+    hipLaunchKernelGGL(k_prio, dim3((unsigned)nb), dim3(256), 0, s, Q);
+    HIPCHK(hipGetLastError());
+  }
+  return LQRO_OK;
+}
+
+// The side stream (plan.nwait workgroups, one a CU): the hot pairs, their
+// hulls, then its share of the row sweep.
+static int enqueue_side(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, const HullArgs& Hh) {
+  const int x_dim = c->cfg.x_dim, nwait = plan.nwait;
+  const dim3 pair_block(P.waves * 64);
+  if (!plan.spec) {   // (speculative builds: the side goes straight to k_qhull)
+    launch_pair(x_dim, dim3(nwait), pair_block, c->lds_bytes, c->side, hot_side(c, plan, P));
+    HIPCHK(hipGetLastError());
+  }
+  if (c->qhull_order) {
+    // the hot pairs' hulls in Qhull's order (k_qhull leaves when the queue
+    // is empty), then the row sweep
+    if (plan.qside) {
+      PairArgs Pq = P;
+      Pq.max_waves = plan.qside_waves;
+      if (plan.nside == 0) Pq.nrows = 0;
+      launch_qside(x_dim, dim3(std::min(nwait, c->qworkers)), c->side, Hh, Pq);
       HIPCHK(hipGetLastError());
-      if (lds_ok) {
-        // the pairs it handed over (rare: near-coplanar input) in the full
-        // hull right away, still beside the sweep (scratch blocks 0..nwait-1;
-        // the k_hull after the sweep uses nwait.. and starts after the side)
-        HullArgs Hf = Hh;
-        Hf.queue = c->d_lq; Hf.count = c->d_hcount + 11; Hf.next = c->d_hcount + 12;
-        launch_hull(dim3(nwait), c->side, Hf);
-        HIPCHK(hipGetLastError());
-      }
-      if (nside > 0) {
-        launch_pair(g.x_dim, dim3(nwait), dim3(P.waves * 64), c->lds_bytes, c->side, P);
-        HIPCHK(hipGetLastError());
-      }
     } else {
-      PairArgs Pt = P;
-      Pt.max_waves = side_waves;
-      if (nside == 0) Pt.nrows = 0;
-      launch_side(g.x_dim, dim3(nwait), dim3(HULL_CTHREADS), c->side, Hh, Pt);
+      if (!c->knobs.qhull_big) {
+        HullArgs Hs = plan.spec ? with_spec(c, Hh) : Hh;
+        if (plan.split) { Hs.prod_done = c->d_hot2 + LQRO_H2_HOT2_DONE; Hs.prod_total = (int)plan.nblk; }
+        launch_qhull(dim3(std::min(nwait, c->qworkers)), c->side, Hs);
+        HIPCHK(hipGetLastError());
+      }
+      if (plan.nside > 0) {
+        launch_pair(x_dim, dim3(nwait), pair_block, c->lds_bytes, c->side, P);
+        HIPCHK(hipGetLastError());
+      }
+    }
+  } else if (c->knobs.local_hull) {
+    // the hot pairs' local hulls (k_lhull leaves when the queue is empty:
+    // later jobs go to the k_lhull after the sweep), then the row sweep
+    launch_lhull(dim3(nwait), c->side, Hh);
+    HIPCHK(hipGetLastError());
+    if (plan.lds_ok) {
+      // the pairs it handed over (rare: near-coplanar input) in the full
+      // hull right away, still beside the sweep (scratch blocks 0..nwait-1;
+      // the k_hull after the sweep uses nwait.. and starts after the side)
+      launch_hull(dim3(nwait), c->side, handed_over(c, Hh));
       HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(c->xev[1], c->side));
-    HIPCHK(hipStreamWaitEvent(s, c->xev[1], 0));
+    if (plan.nside > 0) {
+      launch_pair(x_dim, dim3(nwait), pair_block, c->lds_bytes, c->side, P);
+      HIPCHK(hipGetLastError());
+    }
+  } else {
+    PairArgs Pt = P;
+    Pt.max_waves = plan.side_waves;
+    if (plan.nside == 0) Pt.nrows = 0;
+    launch_side(x_dim, dim3(nwait), dim3(HULL_CTHREADS), c->side, Hh, Pt);
+    HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(c->ev[1], s));
+  return LQRO_OK;
+}
+
+// k_hull on H's queue beside the side's scratch blocks, then k_hull_big for
+// what its LDS could not hold (or, without the LDS hull, for the whole queue)
+static int enqueue_full_hulls(lqro_ctx* c, const StepPlan& plan, HullArgs H, hipStream_t s) {
+  H.block_base = plan.nwait;
+  H.big_main = plan.lds_ok ? 0 : 1;
+  if (plan.lds_ok) {
+    launch_hull(dim3(c->hull_blocks - plan.nwait), s, H);
+    HIPCHK(hipGetLastError());
+  }
+  H.block_base = 0;
+  launch_hull_big(dim3(c->hull_big_blocks), s, H);
+  HIPCHK(hipGetLastError());
+  return LQRO_OK;
+}
+
+// The main stream once the sweep and the side are done: every hull job left.
+static int enqueue_hulls_after_sweep(lqro_ctx* c, const StepPlan& plan, const HullArgs& Hh, hipStream_t s, int phase) {
+  const lqro_config& g = c->cfg;
   if (c->qhull_order) {
     // every hull job left, the ones beyond k_qhull's caps, then the facet-0
     // pairs' loop-carried normals
-    if (spec) {   // (a speculative job not taken on the side)
-      Hh.spec_mark = c->d_hotmark; Hh.spec_n = c->d_hot2 + 5; Hh.spec_next = c->d_hot2 + 6;
-    }
-    if (!c->qhull_big) {
-      launch_qhull(dim3(c->qworkers), s, Hh);
+    HullArgs Hq = plan.spec ? with_spec(c, Hh) : Hh;   // (a speculative job not taken on the side)
+    if (!c->knobs.qhull_big) {
+      launch_qhull(dim3(c->qworkers), s, Hq);
       HIPCHK(hipGetLastError());
     }
-    Hh.big_main = c->qhull_big;
-    launch_qhull_big(dim3(c->qworkers), s, Hh);
+    Hq.big_main = c->knobs.qhull_big;
+    launch_qhull_big(dim3(c->qworkers), s, Hq);
     HIPCHK(hipGetLastError());
-    Hh.big_main = 0;
     // this step's inside-hull pairs head the next step's hot list
-    hipLaunchKernelGGL(k_prio_save, dim3(1), dim3(256), 0, s, c->d_hq, c->d_hcount, c->hull_cap, c->d_prevq,
-                       c->d_hot2, c->hot_cap, spec ? (const unsigned char*)c->d_hotmark : nullptr,
+    hipLaunchKernelGGL(k_prio_save, dim3(1), dim3(256), 0, s, c->d_hq, c->d_hcount + LQRO_HC_HULL, c->hull_cap,
+                       c->d_prevq, c->d_hot2 + LQRO_H2_PREV, c->hot_cap,
+                       plan.spec ? (const unsigned char*)c->d_hotmark : nullptr,
                        (const unsigned long long*)c->d_hbuild, (const unsigned long long*)(c->d_stats + LQRO_ST_NBUILD),
-                       (int)LQRO_HBUILD_CAP, c->d_hotlist, c->d_hot2 + 1, split ? c->d_hotmark : nullptr, slots);
+                       (int)LQRO_HBUILD_CAP, c->d_hotlist, c->d_hot2 + LQRO_H2_HOT1,
+                       plan.split ? c->d_hotmark : nullptr, plan.slots);
     HIPCHK(hipGetLastError());
     if (phase == 0) {
-      launch_stale(s, c->d_planes, c->d_qnrm, c->d_qstale, c->d_hcount + 15, c->hull_cap, d_x, g.x_dim, npr, c->rb,
-                   c->rs, c->d_carry, c->d_recs, slots);
+      launch_stale(s, c->d_planes, c->d_qnrm, c->d_qstale, c->d_hcount + LQRO_HC_FACET0, c->hull_cap, Hh.x, g.x_dim,
+                   plan.npr, c->rb, c->rs, c->d_carry, c->d_recs, plan.slots);
       HIPCHK(hipGetLastError());
     }
-  } else if (c->local_hull) {
+    return LQRO_OK;
+  }
+  if (c->knobs.local_hull) {
     // k_lhull takes the queue k_pair filled; k_hull / k_hull_big then take
     // the pairs it handed over (scratch: hull_blocks blocks of 6 H*NP doubles)
     launch_lhull(dim3(c->hull_blocks), s, Hh);
     HIPCHK(hipGetLastError());
-    Hh.queue = c->d_lq; Hh.count = c->d_hcount + 11; Hh.next = c->d_hcount + 12;
+    return enqueue_full_hulls(c, plan, handed_over(c, Hh), s);
   }
-  if (!c->qhull_order) {
-    Hh.block_base = nwait;
-    Hh.big_main = lds_ok ? 0 : 1;
-    if (lds_ok) {
-      launch_hull(dim3(c->hull_blocks - nwait), s, Hh);
-      HIPCHK(hipGetLastError());
-    }
-    Hh.block_base = 0;
-    launch_hull_big(dim3(c->hull_big_blocks), s, Hh);
+  return enqueue_full_hulls(c, plan, Hh, s);
+}
+
+// phase 0: the whole step.  Row shards in Qhull order split it around the
+// exchange of the loop-carried normal (lqro_step_device_begin / _end):
+// phase 1 runs the sweep and the hulls and writes each own row's last
+// normal into d_rowtab; phase 2 (enqueue_tail) resolves the facet-0 pairs
+// against every rank's rows and runs the LP.
+//
+// persistent: one workgroup per CU (LDS-bound), rows off a queue.
+//   main:  k_prio -> k_pair(rows, n_cu - side blocks) -> [side done] -> k_hull -> k_hull_big -> k_lp
+//   side:  [k_prio done] -> k_pair(hot, side blocks) -> k_side(hot hulls, then rows)
+// The hot launch computes the pairs k_prio predicts to be inside-hull, so
+// their hulls run on the side CUs while the row launch sweeps the rest on
+// the others; each side workgroup joins the sweep as soon as the hull
+// queue is drained.  No kernel waits on another running kernel (streams
+// sharing a hardware queue just serialise), and the two concurrent grids
+// add up to one workgroup per CU.  Hull jobs the prediction missed are
+// taken by the hulls after the sweep.  Which of this a step does is
+// plan_step's decision (lqro_plan.hpp).
+static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, double* d_newv,
+                        hipStream_t s, int phase = 0, double* d_rowtab = nullptr) {
+  const lqro_config& g = c->cfg;
+  if (g.x_dim != 16 && g.x_dim != 12) return LQRO_E_ARG;
+  // 1. the schedule, from the work of the step two before: its copy into the
+  // pinned slot has completed once its event has (the host runs at most one
+  // step ahead of the GPU here), so the schedule does not depend on host/GPU
+  // timing
+  const int slot = (int)(c->nstep & 1);
+  StepFeedback fb = kNoFeedback;
+  if (c->nstep >= 2) {
+    HIPCHK(hipEventSynchronize(c->iev[slot]));
+    fb = c->h_feedback[slot];
+  }
+  double* d_lpnv = d_newv != nullptr ? d_newv : (phase == 1 ? c->d_newv : nullptr);   // the early LP's newV
+  const StepPlan plan = plan_step(step_shape(c, phase, d_lpnv, d_newv), c->knobs, fb, fb.inside != ~0ull);
+  c->early_step = plan.early ? 1 : 0;
+  c->early_internal = plan.early_internal ? 1 : 0;
+  // 2. the kernels' arguments
+  const PairArgs P = pair_args(c, plan, d_x);
+  const HullArgs Hh = hull_args(c, plan, P, d_vgoal, d_lpnv);
+  // 3. the launches
+  if (int rc = enqueue_prologue(c, plan, P, s)) return rc;
+  // the row launch is submitted before the side stream's work: should the two
+  // streams land on one hardware queue (a second context in the process), the
+  // main grid still runs first on its CUs instead of k_side's row tail
+  // sweeping every row on the side CUs alone
+  if (plan.nwait > 0) HIPCHK(hipEventRecord(c->xev[0], s));
+  if (plan.split) {
+    launch_pair(g.x_dim, dim3(plan.nblk), dim3(P.waves * 64), c->lds_bytes, s, hot_main(c, plan, P));
     HIPCHK(hipGetLastError());
   }
+  launch_pair(g.x_dim, dim3(plan.nblk), dim3(P.waves * 64), c->lds_bytes, s, P);
+  HIPCHK(hipGetLastError());
+  if (plan.early) {
+    // the rows the main sweep closed (no open hull): their LP on its CUs
+    // while the side stream's hulls run
+    LpArgs Le = lp_args(c, plan.npr, d_vgoal, d_lpnv);
+    Le.lp4_list = nullptr;
+    Le.rowpend = c->d_rowpend; Le.rowclaim = c->d_rowclaim; Le.row_target = plan.row_target; Le.mode = 1;
+    HIPCHK(hipFuncSetAttribute((const void*)k_lp_lds<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLpLdsMax));
+    hipLaunchKernelGGL(k_lp_lds<8>, dim3((unsigned)c->nrows), dim3(64), (size_t)plan.npr * 32, s, Le);
+    HIPCHK(hipGetLastError());
+  }
+  if (plan.nwait > 0) {
+    HIPCHK(hipStreamWaitEvent(c->side, c->xev[0], 0));
+    if (int rc = enqueue_side(c, plan, P, Hh)) return rc;
+    HIPCHK(hipEventRecord(c->xev[1], c->side));
+    HIPCHK(hipStreamWaitEvent(s, c->xev[1], 0));
+  }
+  HIPCHK(hipEventRecord(c->ev[1], s));
+  if (int rc = enqueue_hulls_after_sweep(c, plan, Hh, s, phase)) return rc;
   HIPCHK(hipEventRecord(c->ev[2], s));
   if (phase == 1) {
     // each own row's last normal (none without Qhull order)
-    launch_rowlast(s, c->qhull_order ? c->d_planes : nullptr, c->d_qnrm, npr, c->nrows, c->rb, c->rs, d_rowtab);
+    launch_rowlast(s, c->qhull_order ? c->d_planes : nullptr, c->d_qnrm, plan.npr, c->nrows, c->rb, c->rs, d_rowtab);
     HIPCHK(hipGetLastError());
     c->pend_x = d_x;
     c->pend_vgoal = d_vgoal;
@@ -1235,27 +1129,6 @@ static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   return enqueue_tail(c, d_x, d_vgoal, d_newv, s, nullptr);
 }
 
-// The side's width in Qhull order from the work measured two steps before:
-// with k side CUs the builds end no sooner than max(b_max, 1.15 w_build / k)
-// (LPT packing of chains, 15 % margin) and the sweep's rows no sooner than
-// w_sweep / (n - k).  The widest k within 2 % of the best such bound: where
-// the builds bound the step (C3: the slowest build) every build keeps a CU
-// of its own as long as the sweep stays shorter; where the sweep does (C5: its
-// 2048-row shard is ~86 CU-s of sweep against ~21 CU-s of builds) the side
-// shrinks to what the builds need (224 -> ~60 CUs: 4.7 s -> ~0.6 s a step).
-static int qhull_side_balance(int n, double w_sweep, double w_build, double b_max) {
-  const int kmax = n - n / 8;
-  double best = 1e300;
-  std::vector<double> t((size_t)kmax + 1, 0.0);
-  for (int k = 1; k <= kmax; ++k) {
-    t[k] = std::max(std::max(b_max, 1.15 * w_build / k), w_sweep / (double)(n - k));
-    best = std::min(best, t[k]);
-  }
-  for (int k = kmax; k >= 1; --k)
-    if (t[k] <= 1.02 * best) return k;
-  return kmax;
-}
-
 static int enqueue_tail(lqro_ctx* c, const double* d_x, const double* d_vgoal, double* d_newv, hipStream_t s,
                         const double* d_rowtab) {
   const lqro_config& g = c->cfg;
@@ -1263,7 +1136,7 @@ static int enqueue_tail(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   const long slots = (long)c->nrows * npr;
   const int slot = (int)(c->nstep & 1);
   if (d_rowtab && c->qhull_order) {
-    launch_stale_rows(s, c->d_planes, c->d_qnrm, c->d_qstale, c->d_hcount + 15, c->hull_cap, d_x, g.x_dim, npr,
+    launch_stale_rows(s, c->d_planes, c->d_qnrm, c->d_qstale, c->d_hcount + LQRO_HC_FACET0, c->hull_cap, d_x, g.x_dim, npr,
                       c->rb, c->rs, d_rowtab, g.n_agents, c->d_carry, c->d_recs, slots);
     HIPCHK(hipGetLastError());
   }
@@ -1279,11 +1152,15 @@ static int enqueue_tail(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
                        c->nrows, c->rb, c->rs, (const double*)c->d_newv, d_newv);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemcpyAsync(c->h_inside + 8 * slot, c->d_stats + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(c->h_inside + 8 * slot + 1, c->d_stats + LQRO_ST_SWORK, 3 * sizeof(unsigned long long),
+  // this step's work, for the schedule of the step two after it
+  StepFeedback* fb = c->h_feedback + slot;
+  static_assert(offsetof(StepFeedback, build_max) - offsetof(StepFeedback, sweep_work) ==
+                    (LQRO_ST_BMAX - LQRO_ST_SWORK) * sizeof(unsigned long long),
+                "LQRO_ST_SWORK, _BWORK, _BMAX in one copy");
+  HIPCHK(hipMemcpyAsync(&fb->inside, c->d_stats + LQRO_ST_INSIDE, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&fb->sweep_work, c->d_stats + LQRO_ST_SWORK, 3 * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(c->h_inside + 8 * slot + 4, c->d_stats + LQRO_ST_RETRY, sizeof(unsigned long long),
-                        hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&fb->retried, c->d_stats + LQRO_ST_RETRY, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   HIPCHK(hipEventRecord(c->iev[slot], s));
   HIPCHK(hipEventRecord(c->ev[3], s));
   c->stepped = 1;
@@ -1346,13 +1223,13 @@ int lqro_step(lqro_ctx* c, const double* x, const double* vgoal, double* newv) {
     }
   }
   int hc = 0;
-  HIPCHK(hipMemcpy(&hc, c->d_hcount, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&hc, c->d_hcount + LQRO_HC_HULL, sizeof(int), hipMemcpyDeviceToHost));
   if (hc > c->hull_cap) return LQRO_E_OVERFLOW;
   // a pair whose hull the kernels could not build has no half-plane: the
   // step says so (the reference always gets a hull from qconvex, LQRO:879-880)
   unsigned long long st[LQRO_ST_FAILS];
   HIPCHK(hipMemcpy(st, c->d_stats, sizeof st, hipMemcpyDeviceToHost));
-  if (st[4]) return LQRO_E_HULL;
+  if (st[LQRO_ST_HULLFAIL]) return LQRO_E_HULL;
   // a pair whose winner qconvex may have merged (Qhull's pre-merge is not
   // restated): never a silent difference from the reference (LQRO:925-967)
   if (st[LQRO_ST_MWIN]) return LQRO_E_QHMERGE;
@@ -1588,7 +1465,7 @@ int lqro_get_stats_ex(lqro_ctx* c, int64_t* st, int32_t n) {
   HIPCHK(wait_last_step(c));
   unsigned long long h[LQRO_ST_FAILS];
   HIPCHK(hipMemcpy(h, c->d_stats, sizeof h, hipMemcpyDeviceToHost));
-  if (c->nbr_k <= 0) h[0] = (unsigned long long)c->nrows * c->npr;   // else k_nbr counted the kept pairs
+  if (c->nbr_k <= 0) h[LQRO_ST_PAIRS] = (unsigned long long)c->nrows * c->npr;   // else k_nbr counted the kept pairs
   // [0..10] the device words; [11] LQRO_REC_QHMERGE_WIN pairs (device word
   // LQRO_ST_MWIN; word 11 counts the failures lqro_get_hull_failures names)
   for (int k = 0; k < n; ++k)
@@ -1679,12 +1556,12 @@ int lqro_debug_local_hull(lqro_ctx* c, long long* out) {
   if (!c || !out) return LQRO_E_ARG;
   HIPCHK(hipSetDevice(c->cfg.device));
   HIPCHK(wait_last_step(c));
-  int h[16];
+  int h[LQRO_HC_WORDS];
   HIPCHK(hipMemcpy(h, c->d_hcount, sizeof h, hipMemcpyDeviceToHost));
   unsigned long long r[16];
-  HIPCHK(hipMemcpy(r, c->d_prof + 32 + 2 * 4096 + 32, sizeof r, hipMemcpyDeviceToHost));
-  out[0] = h[13];
-  out[1] = h[11];
+  HIPCHK(hipMemcpy(r, c->d_prof + LQRO_PROF_LFAIL, sizeof r, hipMemcpyDeviceToHost));
+  out[0] = h[LQRO_HC_LDONE];
+  out[1] = h[LQRO_HC_LHAND];
   for (int k = 0; k < 16; ++k) out[2 + k] = (long long)r[k];
   return LQRO_OK;
 }
@@ -1759,11 +1636,11 @@ int lqro_debug_hull_points(lqro_ctx* c, const double* pts, int32_t n, const doub
       Hh.ext_pts = d_pts; Hh.ext_n = n; Hh.ext_max = fmax;
       Hh.ext_facets = (local == 1 || !facets) ? nullptr : d_f; Hh.ext_nf = d_q + 7;
       Hh.ext_full = local == 2;   // k_qhull: rounded points, then the full-precision ones
-      Hh.qscratch = d_qw; Hh.qstride = qstride; Hh.qnrm = d_qn; Hh.qflags = c->qhull_flags;
+      Hh.qscratch = d_qw; Hh.qstride = qstride; Hh.qnrm = d_qn; Hh.qflags = c->knobs.qhull_flags;
       Hh.qstale = d_q + 14; Hh.qstale_count = d_q + 9; Hh.qstale_cap = 1;
       if (local == 2) {
-        Hh.big_main = c->qhull_big;
-        if (!c->qhull_big) launch_qhull(dim3(1), c->stream, Hh);
+        Hh.big_main = c->knobs.qhull_big;
+        if (!c->knobs.qhull_big) launch_qhull(dim3(1), c->stream, Hh);
         launch_qhull_big(dim3(1), c->stream, Hh);
       }
       else if (local) launch_lhull(dim3(1), c->stream, Hh);
@@ -1818,7 +1695,7 @@ int lqro_debug_local_hull_jobs(lqro_ctx* c, unsigned long long* out) {
   if (!c || !out) return LQRO_E_ARG;
   HIPCHK(hipSetDevice(c->cfg.device));
   HIPCHK(wait_last_step(c));
-  HIPCHK(hipMemcpy(out, c->d_prof + 32 + 2 * 4096 + 48, sizeof(unsigned long long) * 4 * 4096, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, c->d_prof + LQRO_PROF_LJOBS, sizeof(unsigned long long) * 4 * 4096, hipMemcpyDeviceToHost));
   return LQRO_OK;
 }
 
