@@ -199,6 +199,60 @@ int lqro_set_gains(lqro_ctx* ctx, const double* A, const double* B,
  * results against the reference.  max_neighbors <= 0 restores all pairs. */
 int lqro_set_neighbors(lqro_ctx* ctx, double neighbor_dist, int32_t max_neighbors);
 
+/* ---- opt-in constraints that are not agents ---------------------------
+ * The reference's LP sees the N-1 pair planes only.  The three calls below
+ * put extra half-planes AHEAD of them in each row's orcaPlanes_, the way
+ * RVO2's Agent::computeNewVelocity puts its obstacle lines before the agent
+ * lines of the same LP (Agent.cpp:84-151; there is no counterpart in LQRO).
+ * Row agent i's plane list becomes: its fence planes (0..6), then its user
+ * planes in the order given, then the pair planes exactly as before;
+ * calculateNewV (LQRO:1223-1234) runs over that list unchanged.  A velocity
+ * v satisfies a plane when normal.(v - point) >= 0, in the agent's absolute
+ * velocity space (the LP's own convention, LQRO:1083).  Extra planes are as
+ * soft as every other plane (linearProgram4 relaxes them like the rest);
+ * inputs must be finite.  Pair records, stats, the hull queue and the
+ * carried normal do not see them.  All arrays are indexed by the global
+ * agent id, so every row shard takes the same arrays and reads its own rows.
+ * With nothing set the step is the reference's; once set, results CHANGE
+ * against the reference.  Each call returns LQRO_E_STATE while a
+ * lqro_step_device_begin is pending, and waits for the last enqueued step
+ * before it replaces a buffer. */
+
+/* User half-planes, host arrays (copied): agent i owns
+ * planes[6*offsets[i] .. 6*offsets[i+1]), six floats a plane (point xyz,
+ * normal xyz: lqro_calculate_new_v's layout); offsets has n_agents + 1
+ * entries.  planes == NULL clears.  Decreasing offsets or more than 8192
+ * planes for one agent: LQRO_E_ARG.  Stands in for RVO2's obstacle-first
+ * plane order (AGT:84-151). */
+int lqro_set_user_planes(lqro_ctx* ctx, const float* planes, const int64_t* offsets);
+
+/* The same, device-resident at a fixed pitch: agent i's planes start at
+ * d_planes + 6*max_per_agent*i and d_counts[i] <= max_per_agent of them are
+ * live (d_counts == NULL: all; a count outside [0, max_per_agent] is
+ * clamped).  The pointers are read when the row's LP runs: the caller keeps
+ * them alive and writes them on the stream the step is enqueued on, before
+ * the step — the path for planes that change every step.  max_per_agent <= 0
+ * clears; above 8192: LQRO_E_ARG.  lqro_set_user_planes builds this layout
+ * in buffers of the context's own.  Stands in for RVO2's obstacle-first
+ * plane order (AGT:84-151). */
+int lqro_set_user_planes_device(lqro_ctx* ctx, const float* d_planes, int32_t max_per_agent,
+                                const int32_t* d_counts);
+
+/* An axis-aligned box [lo, hi] the agents' ellipsoids should stay inside,
+ * with time horizon tau seconds; stands in for RVO2's obstacle-first plane
+ * order (AGT:84-151) with the box's faces as the obstacles.  Every step
+ * writes, for each own row i, axis a = x, y, z in that order, first the
+ * lower face, then the upper:
+ *   lower: normal = +e_a, point[a] = (float)(((lo[a] + m[a]) - p[a]) / tau)
+ *   upper: normal = -e_a, point[a] = (float)(((hi[a] - m[a]) - p[a]) / tau)
+ * (the point's other components +0), p = x[i][0..2] of the step's x, m =
+ * (xy_radius, xy_radius, z_radius); fp64 in exactly that order, rounded
+ * once.  A face whose bound is +-infinity is not emitted (lo = (-inf, -inf,
+ * 0), hi = +inf: a floor alone), so every agent has the same number of fence
+ * planes.  tau <= 0 or lo/hi == NULL turns the fence off; lo[a] + 2 m[a] >
+ * hi[a]: LQRO_E_ARG. */
+int lqro_set_fence(lqro_ctx* ctx, const double lo[3], const double hi[3], double tau);
+
 /* One control step: the pair loop LQRO:1393-1436 for the context's rows.
  * x: n_agents*X agent states (Quadrotor::x), vgoal: n_agents*3,
  * newv: n_agents*3 (only rows [row_begin,row_end) are written).  Host

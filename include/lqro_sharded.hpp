@@ -156,6 +156,22 @@ class ShardedSimulator {
     check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
   }
 
+  // Simulator::setFence / setUserPlanes for this rank's context (the arrays
+  // are indexed by the global agent id: every rank passes the same ones)
+  void setFence(const std::array<double, 3>& lo, const std::array<double, 3>& hi, double tau) {
+    if (ctx_) check(lqro_set_fence(ctx_, lo.data(), hi.data(), tau), "lqro_set_fence");
+  }
+  void setUserPlanes(const std::vector<std::vector<Plane>>& planes) {
+    if (!ctx_) return;
+    if (planes.empty()) return check(lqro_set_user_planes(ctx_, nullptr, nullptr), "lqro_set_user_planes");
+    if (planes.size() != q_.size()) throw Error("setUserPlanes: one list per agent", LQRO_E_ARG);
+    std::vector<float> flat;
+    std::vector<int64_t> offs;
+    flatten_planes(planes, flat, offs);
+    flat.resize(std::max<size_t>(flat.size(), 6));
+    check(lqro_set_user_planes(ctx_, flat.data(), offs.data()), "lqro_set_user_planes");
+  }
+
   // One iteration of LQRO:1393-1446 for this rank's rows, then the state
   // exchange; returns the next seed of the rand() stream.  Enqueued only:
   // download() waits for it.

@@ -69,6 +69,25 @@ struct Quadrotor {
   }
 };
 
+// One extra half-plane of an agent's LP (lqro_set_user_planes): a velocity v
+// satisfies it when normal.(v - point) >= 0.
+struct Plane { float point[3], normal[3]; };
+static_assert(sizeof(Plane) == 6 * sizeof(float), "Plane is lqro_set_user_planes' six floats");
+
+// per-agent plane lists as lqro_set_user_planes' flat arrays
+inline void flatten_planes(const std::vector<std::vector<Plane>>& planes, std::vector<float>& flat,
+                           std::vector<int64_t>& offsets) {
+  offsets.assign(planes.size() + 1, 0);
+  flat.clear();
+  for (size_t i = 0; i < planes.size(); ++i) {
+    for (const Plane& p : planes[i]) {
+      flat.insert(flat.end(), p.point, p.point + 3);
+      flat.insert(flat.end(), p.normal, p.normal + 3);
+    }
+    offsets[i + 1] = offsets[i] + (int64_t)planes[i].size();
+  }
+}
+
 class Simulator {
  public:
   // qlist is held by reference, as the reference's qlist of Quadrotor*.
@@ -102,6 +121,26 @@ class Simulator {
       q.L = q_[0].L; q.E = q_[0].E; q.l = q_[0].l; q.Lh = q_[0].Lh; q.Eh = q_[0].Eh;
     }
     check(lqro_set_gains(ctx_, A_.data(), B_.data(), q_[0].L.data(), q_[0].E.data(), 0), "lqro_set_gains");
+  }
+
+  // Opt-in constraints that are not agents, ahead of the pair planes in each
+  // agent's LP (RVO2's obstacle-first order, AGT:84-151; no counterpart in
+  // LQRO, so results change against the reference once set).  setFence: an
+  // axis-aligned box the ellipsoids should stay inside within tau seconds
+  // (lqro_set_fence; an infinite bound emits no face, tau <= 0 turns it off).
+  // setUserPlanes: one list per agent, empty lists allowed; an empty vector
+  // clears (lqro_set_user_planes).
+  void setFence(const std::array<double, 3>& lo, const std::array<double, 3>& hi, double tau) {
+    check(lqro_set_fence(ctx_, lo.data(), hi.data(), tau), "lqro_set_fence");
+  }
+  void setUserPlanes(const std::vector<std::vector<Plane>>& planes) {
+    if (planes.empty()) return check(lqro_set_user_planes(ctx_, nullptr, nullptr), "lqro_set_user_planes");
+    if (planes.size() != q_.size()) throw Error("setUserPlanes: one list per agent", LQRO_E_ARG);
+    std::vector<float> flat;
+    std::vector<int64_t> offs;
+    flatten_planes(planes, flat, offs);
+    flat.resize(std::max<size_t>(flat.size(), 6));   // (never a null array: NULL means clear)
+    check(lqro_set_user_planes(ctx_, flat.data(), offs.data()), "lqro_set_user_planes");
   }
 
   // The pair loop LQRO:1393-1436 on the GPU: every Quadrotor::newV.

@@ -88,10 +88,12 @@ __device__ __forceinline__ void st_plane(float* base, int i, v3 pt, v3 nm) {
 
 // orcaPlanes_ in push order (j order, LQRObstacles.cpp:1220): a row's plane
 // slots (k_pair's 32-B records, [6] = 1 for a plane) compacted into `planes`
-// (stride PS); returns their count
+// (stride PS) behind the m0 planes the caller staged at its head (lp_head:
+// the row's fence and user planes, RVO2's obstacle-first order, AGT:84-151);
+// returns the list's length.  The closing fence publishes the head too.
 template <int PS>
-__device__ __forceinline__ int lp_compact(const float* src, int npr, float* planes, int lane) {
-  int m = 0;
+__device__ __forceinline__ int lp_compact(const float* src, int npr, float* planes, int lane, int m0 = 0) {
+  int m = m0;
   for (int base = 0; base < npr; base += 64) {
     const int sidx = base + lane;
     float4 a = make_float4(0, 0, 0, 0), b = make_float4(0, 0, 0, 0);
@@ -111,6 +113,18 @@ __device__ __forceinline__ int lp_compact(const float* src, int npr, float* plan
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   return m;
+}
+
+// The head of a row's plane list: nf fence planes (k_fence's, 6 floats a
+// plane) and nu user planes (6 floats a plane), in that order, one plane a
+// lane.  No fence of its own: lp_compact's makes it visible to the wave.
+template <int PS>
+__device__ __forceinline__ void lp_head(const float* fence, int nf, const float* user, int nu, float* planes,
+                                        int lane) {
+  for (int p = lane; p < nf + nu; p += 64) {
+    const float* s = p < nf ? fence + 6 * (size_t)p : user + 6 * (size_t)(p - nf);
+    st_plane<PS>(planes, p, V3(s[0], s[1], s[2]), V3(s[3], s[4], s[5]));
+  }
 }
 
 // lane k's value of x (k uniform): the result is wave-uniform

@@ -125,6 +125,7 @@ struct StepShape {
   size_t lp_lds_max;         // kLpLdsMax
   int early_lp_max_npr;      // LQRO_EARLY_LP_MAX_NPR
   int row_big;               // LQRO_ROW_BIG
+  int extra_planes = 0;      // fence + user planes a row's LP may get ahead of its pair planes (capacity per row)
 };
 
 struct StepPlan {
@@ -267,7 +268,7 @@ inline StepPlan plan_step(const StepShape& S, const StepKnobs& K, const StepFeed
   // to the context's own buffer, copied into the caller's by _end; rows with
   // a facet-0 pair wait for the row-normal exchange in the tail as before)
   const bool early = hot && K.early_lp && S.qhull_order && !K.qhull_big && S.phase != 2 && S.nbr_k <= 0 &&
-                     (size_t)npr * 32 <= S.lp_lds_max && S.has_newv;
+                     ((size_t)npr + (size_t)S.extra_planes) * 32 <= S.lp_lds_max && S.has_newv;
   p.early = early;
   p.early_internal = early && !S.newv_is_callers;
   const int units = S.nrows * p.row_split;
@@ -292,7 +293,9 @@ inline StepPlan plan_step(const StepShape& S, const StepKnobs& K, const StepFeed
   // (k_qhull's in-place rebuild of capped builds where they happen: hulls of
   // more than 10,000 points (C5's ~19,000), or builds capped two steps before)
   p.big_inline = K.qhull_inline && !K.qhull_big && (S.hnp > 10000 || retried_prev > 0) ? 1 : 0;
-  p.row_lp = npr <= S.early_lp_max_npr ? 1 : 0;
+  // (a row with fence or user planes: k_qhull's in-job LP knows the pair
+  // planes only, so the job that closes the row leaves it to the tail)
+  p.row_lp = npr <= S.early_lp_max_npr && S.extra_planes <= 0 ? 1 : 0;
   p.row_target = p.row_split * S.row_big;
   return p;
 }

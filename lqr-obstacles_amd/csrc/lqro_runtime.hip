@@ -185,10 +185,21 @@ __global__ void __launch_bounds__(256) k_tables(int X, int U, int H, const doubl
 // ---------------------------------------------------------------------------
 struct LpArgs {
   int npr, nrows, row_begin, row_stride;
+  // a row's plane list holds at most cap = npr + nfence + umax planes; npr
+  // stays the number of pair slots to compact (no extras: cap == npr)
+  int cap;
   double vmax;
   const float* slots;   // per row npr x 8 (flag in [6]: 1 = plane)
-  float* compact;       // per row npr x 8: emitted planes in j order
-  float* proj;          // per row npr x 8: linearProgram4's projected planes
+  float* compact;       // per row cap x 8: the row's planes in push order
+  float* proj;          // per row cap x 8: linearProgram4's projected planes
+  // the planes ahead of the pair planes (RVO2's obstacle-first order,
+  // AGT:84-151): k_fence's, per own row nfence x 6 floats, then the user's,
+  // per agent (global id) umax x 6 floats of which ucounts[i] are live
+  // (null: all)
+  const float* fence;
+  const float* uplanes;
+  const int* ucounts;
+  int nfence, umax;
   const double* vgoal;
   double* newv;
   unsigned long long* prof;   // LQRO_LP_PROFILE: cycles per row
@@ -210,21 +221,28 @@ struct LpArgs {
 template <int PS>
 __device__ __forceinline__ void lp_row(const LpArgs& A, int lrow, float* planes, int lane) {
   const int i = A.row_begin + lrow * A.row_stride;
-  const int m = lp_compact<PS>(A.slots + (size_t)lrow * A.npr * 8, A.npr, planes, lane);
+  int m0 = 0;
+  if (A.cap != A.npr) {
+    const int nu = A.umax <= 0 ? 0 : A.ucounts ? max(0, min(A.ucounts[i], A.umax)) : A.umax;
+    lp_head<PS>(A.fence + (size_t)lrow * A.nfence * 6, A.nfence, A.uplanes + (size_t)i * A.umax * 6, nu, planes,
+                lane);
+    m0 = A.nfence + nu;
+  }
+  const int m = lp_compact<PS>(A.slots + (size_t)lrow * A.npr * 8, A.npr, planes, lane, m0);
   const v3 pref = V3((float)A.vgoal[3 * i], (float)A.vgoal[3 * i + 1], (float)A.vgoal[3 * i + 2]);
   v3 nv = V3(0.0f, 0.0f, 0.0f);
   const int fail = w_lp3<PS>(planes, m, A.vmax, pref, false, nv, lane);          // :1228
 #ifdef LQRO_LP_PROFILE
   int lp4_iters = 0;
   if (fail < m)
-    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.npr * PS, lane, lp4_iters);
+    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.cap * PS, lane, lp4_iters);
   if (lane == 0 && A.prof && lrow < 4096) A.prof[32 + 4096 + lrow] = ((unsigned long long)m << 40) |
                                                ((unsigned long long)fail << 20) | (unsigned)lp4_iters;
 #else
   if (fail < m && A.lp4_list != nullptr) {
     // linearProgram4 (:1230) in k_lp4, with its projected planes in LDS too:
     // hand over the compacted planes (stride PS) and linearProgram3's result
-    float* dst = A.compact + (size_t)lrow * A.npr * 8;
+    float* dst = A.compact + (size_t)lrow * A.cap * 8;
     if (dst != planes)
       for (int q = lane; q < PS * m; q += 64) dst[q] = planes[q];
     if (lane == 0) {
@@ -236,7 +254,7 @@ __device__ __forceinline__ void lp_row(const LpArgs& A, int lrow, float* planes,
     return;
   }
   if (fail < m)
-    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.npr * PS, lane);  // :1230
+    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.cap * PS, lane);  // :1230
 #endif
   if (lane == 0) {
     A.newv[3 * i] = nv.x;
@@ -250,7 +268,7 @@ __global__ void __launch_bounds__(256) k_lp(LpArgs A) {
   const int lane = threadIdx.x & 63;
   const int lrow = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (lrow >= A.nrows) return;
-  lp_row<8>(A, lrow, A.compact + (size_t)lrow * A.npr * 8, lane);
+  lp_row<8>(A, lrow, A.compact + (size_t)lrow * A.cap * 8, lane);
 }
 
 // one wave per workgroup, the row's plane list in LDS (the LP rescans it for
@@ -300,9 +318,9 @@ __global__ void __launch_bounds__(64) k_lp4(LpArgs A, int proj_in_lds) {
     if (job >= *A.lp4_count) return;
     const int* e = A.lp4_list + 6 * (size_t)job;
     const int lrow = e[0], fail = e[1], m = e[2];
-    float* proj = proj_in_lds ? lp4_sm + (size_t)A.npr * PS : A.proj + (size_t)lrow * A.npr * PS;
+    float* proj = proj_in_lds ? lp4_sm + (size_t)A.cap * PS : A.proj + (size_t)lrow * A.cap * PS;
     v3 nv = V3(__int_as_float(e[3]), __int_as_float(e[4]), __int_as_float(e[5]));
-    const float* src = A.compact + (size_t)lrow * A.npr * 8;
+    const float* src = A.compact + (size_t)lrow * A.cap * 8;
     for (int q = lane; q < PS * m; q += 64) planes[q] = src[q];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -336,9 +354,39 @@ __global__ void __launch_bounds__(256) k_copy_claimed(const int* rowclaim, int n
   dst[3 * i + 2] = src[3 * i + 2];
 }
 
+// The fence (lqro_set_fence): an axis-aligned box [lo, hi] the agents'
+// ellipsoids (semi-axes m) should stay inside, as at most six half-planes per
+// own row in absolute velocity space, ahead of the user and pair planes
+// (RVO2 puts its obstacle lines first in the same LP, AGT:84-151).  Axis x,
+// y, z, lower face then upper; a face at infinity is not emitted (`faces`).
+// The bound is fp64 in the order written, rounded once.
+struct FenceArgs {
+  int nrows, row_begin, row_stride, X, nfence, faces;
+  double lo[3], hi[3], m[3], tau;
+  const double* x;
+  float* out;
+};
+__global__ void __launch_bounds__(256) k_fence(FenceArgs F) {
+  const int lrow = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lrow >= F.nrows) return;
+  const size_t i = (size_t)F.row_begin + (size_t)lrow * F.row_stride;
+  float* o = F.out + (size_t)lrow * F.nfence * 6;
+  for (int a = 0; a < 3; ++a) {
+    const double p = F.x[i * F.X + a];
+    for (int side = 0; side < 2; ++side) {
+      if (!((F.faces >> (2 * a + side)) & 1)) continue;
+      const double b = side == 0 ? ((F.lo[a] + F.m[a]) - p) / F.tau : ((F.hi[a] - F.m[a]) - p) / F.tau;
+      for (int q = 0; q < 6; ++q) o[q] = 0.0f;
+      o[a] = (float)b;
+      o[3 + a] = side == 0 ? 1.0f : -1.0f;
+      o += 6;
+    }
+  }
+}
+
 template <int PS>
 static hipError_t launch_lp_lds(LpArgs La, hipStream_t s) {
-  const size_t lds = (size_t)La.npr * 4 * PS;
+  const size_t lds = (size_t)La.cap * 4 * PS;
   hipError_t e = hipFuncSetAttribute((const void*)k_lp_lds<PS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)kLpLdsMax);
   if (e != hipSuccess) return e;
@@ -355,8 +403,8 @@ static hipError_t launch_lp_lds(LpArgs La, hipStream_t s) {
 
 // La.lp4_count / lp4_next must be zero (or lp4_list null)
 static hipError_t launch_lp(LpArgs La, hipStream_t s) {
-  if ((size_t)La.npr * 32 <= 64 * 1024) return launch_lp_lds<8>(La, s);
-  if ((size_t)La.npr * 24 <= kLpLdsMax) return launch_lp_lds<6>(La, s);
+  if ((size_t)La.cap * 32 <= 64 * 1024) return launch_lp_lds<8>(La, s);
+  if ((size_t)La.cap * 24 <= kLpLdsMax) return launch_lp_lds<6>(La, s);
   La.lp4_list = nullptr;
   hipLaunchKernelGGL(k_lp, dim3((unsigned)((La.nrows + 3) / 4)), dim3(256), 0, s, La);
   return hipGetLastError();
@@ -431,6 +479,18 @@ struct lqro_ctx {
   int early_internal;        // ... into d_newv (lqro_step_device_begin: the caller's buffer comes with _end)
   int* d_rowpend;
   int* d_rowclaim;
+  // the planes ahead of a row's pair planes (lqro_set_fence,
+  // lqro_set_user_planes[_device]); lp_cap: the pitch d_lpscratch and
+  // d_lpcompact are allocated for (>= npr + nfence + uplane_max)
+  int nfence, fence_faces;        // faces emitted; bit 2 a + side (side 1 = upper)
+  double fence_lo[3], fence_hi[3], fence_tau;
+  float* d_fence;                 // nrows x nfence x 6, k_fence's output
+  const float* d_uplanes;         // the caller's, or d_uown
+  const int* d_ucounts;           // the caller's, d_ucown, or null
+  int uplane_max;
+  float* d_uown;                  // lqro_set_user_planes's copies
+  int* d_ucown;
+  int lp_cap;
   PairArgs pa;
 };
 
@@ -454,7 +514,7 @@ static hipError_t wait_last_step(lqro_ctx* c) {
 
 extern "C" {
 
-int lqro_version(void) { return 1; }
+int lqro_version(void) { return 2; }
 
 const char* lqro_status_string(int s) {
   switch (s) {
@@ -499,7 +559,7 @@ void lqro_destroy(lqro_ctx* c) {
                 c->d_L, c->d_E, c->d_planes, c->d_lpscratch, c->d_lpcompact, c->d_recs, c->d_hq, c->d_hcount,
                 c->d_err, c->d_hfaces, c->d_hscratch, c->d_hiscratch, c->d_hfscratch, c->d_stats, c->d_prof, c->d_rq, c->d_hbig, c->d_hwide, c->d_hbag, c->d_lp4, c->d_hotlist, c->d_hotmark, c->d_nbrlist, c->d_hfbest, c->d_hvpid, c->d_hstack, c->d_lq,
                 c->d_qscratch, c->d_qnrm, c->d_qstale, c->d_hbuild, c->d_carry, c->d_rowpend /* d_rowclaim inside */,
-                c->d_prevq, c->d_hot2};
+                c->d_prevq, c->d_hot2, c->d_fence, c->d_uown, c->d_ucown};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   for (int k = 0; k < 5; ++k)
@@ -631,6 +691,7 @@ int lqro_create(const lqro_config* cfg, lqro_ctx** out) {
   if (c->rb < 0 || c->re > g.n_agents || c->rb >= c->re || g.row_stride < 0) { delete c; return LQRO_E_ARG; }
   c->nrows = (c->re - c->rb + c->rs - 1) / c->rs;
   c->npr = g.n_agents - 1;
+  c->lp_cap = c->npr;
   // LDS layout of k_pair (in doubles): block tables, then one region per wave
   const int H = g.horizon, NP = g.n_points, X = g.x_dim, XP = X + 1;
   if (NP > 64 * kMaxPW || H > 64 * kMaxKS) { delete c; return LQRO_E_ARG; }
@@ -723,6 +784,116 @@ int lqro_set_neighbors(lqro_ctx* c, double neighbor_dist, int32_t max_neighbors)
   return LQRO_OK;
 }
 
+constexpr int kMaxUserPlanes = 8192;   // per agent
+
+// the LP scratch at a pitch of npr + extra planes per row; only grows, and
+// never in a step.  The caller has waited for the last step.
+static int lp_scratch_reserve(lqro_ctx* c, int extra) {
+  const int cap = c->npr + extra;
+  if (cap <= c->lp_cap) return LQRO_OK;
+  const size_t bytes = sizeof(float) * 8 * (size_t)c->nrows * (size_t)cap;
+  float *a = nullptr, *b = nullptr;
+  if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) {
+    if (a) (void)hipFree(a);
+    return LQRO_E_NOMEM;
+  }
+  (void)hipFree(c->d_lpscratch);
+  (void)hipFree(c->d_lpcompact);
+  c->d_lpscratch = a; c->d_lpcompact = b; c->lp_cap = cap;
+  return LQRO_OK;
+}
+
+// the user planes' fixed-pitch device layout becomes the context's; `own`:
+// the context's copies (lqro_set_user_planes), freed when replaced
+static int set_user_layout(lqro_ctx* c, const float* d_planes, int maxp, const int* d_counts, float* own,
+                           int* cown) {
+  if (maxp > 0)
+    if (int rc = lp_scratch_reserve(c, c->nfence + maxp)) return rc;
+  if (c->d_uown) (void)hipFree(c->d_uown);
+  if (c->d_ucown) (void)hipFree(c->d_ucown);
+  c->d_uown = own; c->d_ucown = cown;
+  c->d_uplanes = maxp > 0 ? d_planes : nullptr;
+  c->d_ucounts = maxp > 0 ? d_counts : nullptr;
+  c->uplane_max = maxp > 0 ? maxp : 0;
+  return LQRO_OK;
+}
+
+int lqro_set_user_planes_device(lqro_ctx* c, const float* d_planes, int32_t max_per_agent, const int32_t* d_counts) {
+  if (!c) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;   // the pending half-step's LP still reads them
+  if (max_per_agent > kMaxUserPlanes || (max_per_agent > 0 && !d_planes)) return LQRO_E_ARG;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  HIPCHK(wait_last_step(c));
+  return set_user_layout(c, d_planes, max_per_agent, d_counts, nullptr, nullptr);
+}
+
+int lqro_set_user_planes(lqro_ctx* c, const float* planes, const int64_t* offsets) {
+  if (!c) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;
+  if (planes && !offsets) return LQRO_E_ARG;
+  const size_t N = (size_t)c->cfg.n_agents;
+  int64_t maxp = 0;
+  if (planes)
+    for (size_t i = 0; i < N; ++i) {
+      const int64_t m = offsets[i + 1] - offsets[i];
+      if (m < 0 || m > kMaxUserPlanes) return LQRO_E_ARG;
+      maxp = std::max(maxp, m);
+    }
+  HIPCHK(hipSetDevice(c->cfg.device));
+  HIPCHK(wait_last_step(c));
+  if (maxp == 0) return set_user_layout(c, nullptr, 0, nullptr, nullptr, nullptr);
+  // the same layout lqro_set_user_planes_device takes, in buffers of the context's own
+  std::vector<float> h(N * (size_t)maxp * 6, 0.0f);
+  std::vector<int> cnt(N);
+  for (size_t i = 0; i < N; ++i) {
+    cnt[i] = (int)(offsets[i + 1] - offsets[i]);
+    if (cnt[i]) memcpy(&h[i * (size_t)maxp * 6], planes + 6 * offsets[i], sizeof(float) * 6 * (size_t)cnt[i]);
+  }
+  float* own = nullptr;
+  int* cown = nullptr;
+  if (hipMalloc(&own, sizeof(float) * h.size()) != hipSuccess || hipMalloc(&cown, sizeof(int) * N) != hipSuccess) {
+    if (own) (void)hipFree(own);
+    return LQRO_E_NOMEM;
+  }
+  int rc = LQRO_OK;
+  if (hipMemcpy(own, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(cown, cnt.data(), sizeof(int) * N, hipMemcpyHostToDevice) != hipSuccess)
+    rc = LQRO_E_HIP;
+  // (the stream the step reads them on may be non-blocking: the copies above are synchronous)
+  if (rc == LQRO_OK) rc = set_user_layout(c, own, (int)maxp, cown, own, cown);
+  if (rc != LQRO_OK) { (void)hipFree(own); (void)hipFree(cown); }   // (a failed call leaves the old planes in place)
+  return rc;
+}
+
+int lqro_set_fence(lqro_ctx* c, const double* lo, const double* hi, double tau) {
+  if (!c) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;
+  const lqro_config& g = c->cfg;
+  int faces = 0, n = 0;
+  if (lo && hi && tau > 0) {
+    for (int a = 0; a < 3; ++a) {
+      const double m = a < 2 ? g.xy_radius : g.z_radius;
+      if (lo[a] + 2 * m > hi[a]) return LQRO_E_ARG;   // (NaN bounds are outside the contract)
+      if (!std::isinf(lo[a])) { faces |= 1 << (2 * a); ++n; }
+      if (!std::isinf(hi[a])) { faces |= 1 << (2 * a + 1); ++n; }
+    }
+  }
+  HIPCHK(hipSetDevice(g.device));
+  HIPCHK(wait_last_step(c));
+  if (n > 0) {
+    if (int rc = lp_scratch_reserve(c, n + c->uplane_max)) return rc;
+    if (!c->d_fence && hipMalloc(&c->d_fence, sizeof(float) * 36 * (size_t)c->nrows) != hipSuccess) {
+      c->d_fence = nullptr;
+      return LQRO_E_NOMEM;
+    }
+    for (int a = 0; a < 3; ++a) { c->fence_lo[a] = lo[a]; c->fence_hi[a] = hi[a]; }
+    c->fence_tau = tau;
+  }
+  c->nfence = n;
+  c->fence_faces = faces;
+  return LQRO_OK;
+}
+
 int lqro_set_gains(lqro_ctx* c, const double* A, const double* B, const double* L,
                    const double* E, int32_t per_agent) {
   if (!c || !A || !B || !L || !E) return LQRO_E_ARG;
@@ -758,10 +929,12 @@ static int enqueue_tail(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
 // k_lp4 list)
 static LpArgs lp_args(const lqro_ctx* c, int npr, const double* d_vgoal, double* d_newv) {
   LpArgs La{};
-  La.npr = npr; La.nrows = c->nrows; La.row_begin = c->rb; La.row_stride = c->rs; La.vmax = c->cfg.vmax_lp;
+  La.npr = npr; La.cap = npr + c->nfence + c->uplane_max; La.nrows = c->nrows; La.row_begin = c->rb; La.row_stride = c->rs; La.vmax = c->cfg.vmax_lp;
   La.slots = c->d_planes; La.compact = c->d_lpcompact; La.proj = c->d_lpscratch;
   La.vgoal = d_vgoal; La.newv = d_newv; La.prof = c->d_prof;
   La.lp4_list = c->d_lp4; La.lp4_count = c->d_hcount + LQRO_HC_LP4; La.lp4_next = c->d_hcount + LQRO_HC_LP4_NEXT;
+  La.fence = c->d_fence; La.nfence = c->nfence;
+  La.uplanes = c->d_uplanes; La.ucounts = c->d_ucounts; La.umax = c->uplane_max;
   return La;
 }
 
@@ -777,6 +950,7 @@ static StepShape step_shape(const lqro_ctx* c, int phase, const double* d_lpnv, 
   S.hull_lds_max_hnp = kHullLdsMaxHNP; S.hull_lds_doubles = sizeof(HullMemC) / 8; S.hull_cwaves = HULL_CWAVES;
   S.qhull_lds_doubles = qhull_lds_doubles(); S.lp_lds_max = kLpLdsMax;
   S.early_lp_max_npr = LQRO_EARLY_LP_MAX_NPR; S.row_big = LQRO_ROW_BIG;
+  S.extra_planes = c->nfence + c->uplane_max;
   return S;
 }
 
@@ -922,6 +1096,17 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
     HIPCHK(hipGetLastError());
   }
   if (plan.early) HIPCHK(hipMemsetAsync(c->d_rowpend, 0, sizeof(int) * 2 * (size_t)c->nrows, s));
+  if (c->nfence > 0) {   // this step's fence planes, before any LP can start
+    FenceArgs F{};
+    F.nrows = c->nrows; F.row_begin = c->rb; F.row_stride = c->rs; F.X = g.x_dim;
+    F.nfence = c->nfence; F.faces = c->fence_faces; F.tau = c->fence_tau;
+    for (int a = 0; a < 3; ++a) {
+      F.lo[a] = c->fence_lo[a]; F.hi[a] = c->fence_hi[a]; F.m[a] = a < 2 ? g.xy_radius : g.z_radius;
+    }
+    F.x = P.x; F.out = c->d_fence;
+    hipLaunchKernelGGL(k_fence, dim3((unsigned)((c->nrows + 255) / 256)), dim3(256), 0, s, F);
+    HIPCHK(hipGetLastError());
+  }
   if (plan.hot) {
     const PrioArgs Q = prio_args(c, plan, P);
     if (plan.split) {
@@ -1104,7 +1289,7 @@ static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
     Le.lp4_list = nullptr;
     Le.rowpend = c->d_rowpend; Le.rowclaim = c->d_rowclaim; Le.row_target = plan.row_target; Le.mode = 1;
     HIPCHK(hipFuncSetAttribute((const void*)k_lp_lds<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLpLdsMax));
-    hipLaunchKernelGGL(k_lp_lds<8>, dim3((unsigned)c->nrows), dim3(64), (size_t)plan.npr * 32, s, Le);
+    hipLaunchKernelGGL(k_lp_lds<8>, dim3((unsigned)c->nrows), dim3(64), (size_t)Le.cap * 32, s, Le);
     HIPCHK(hipGetLastError());
   }
   if (plan.nwait > 0) {
@@ -1414,7 +1599,7 @@ int lqro_calculate_new_v(const float* planes, const int64_t* offsets, int32_t n_
     rc = LQRO_E_HIP;
   } else {
     LpArgs La{};
-    La.npr = (int)mmax; La.nrows = n_agents; La.row_begin = 0; La.row_stride = 1; La.vmax = vmax_lp;
+    La.npr = (int)mmax; La.cap = (int)mmax; La.nrows = n_agents; La.row_begin = 0; La.row_stride = 1; La.vmax = vmax_lp;
     La.slots = d_slots; La.compact = d_compact; La.proj = d_proj; La.vgoal = d_vg; La.newv = d_nv; La.prof = nullptr;
     La.lp4_list = d_l4; La.lp4_count = d_l4c; La.lp4_next = d_l4c + 1;
     if (launch_lp(La, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||

@@ -85,6 +85,7 @@ EXPORTS = (
     "lqro_set_carry_normal", "lqro_get_carry_normal",
     "lqro_step_device_begin", "lqro_step_device_end",
     "lqro_get_stats_ex", "lqro_get_hull_failures", "lqro_get_hull_builds", "lqro_get_qhmerge_pairs",
+    "lqro_set_user_planes", "lqro_set_user_planes_device", "lqro_set_fence",
 )
 
 NORMALS_PER_AGENT = 22   # LQRO_NORMALS_PER_AGENT: 16 propagate + 6 observation
@@ -136,6 +137,9 @@ def lib() -> C.CDLL:
         L.lqro_dynamics_step_device.argtypes = [vp, i32, i32, i32, C.POINTER(Agents), vp]
         L.lqro_normals.argtypes = [C.POINTER(C.c_uint32), i64, vp]
         L.lqro_set_neighbors.argtypes = [vp, dbl, i32]
+        L.lqro_set_user_planes.argtypes = [vp, vp, vp]
+        L.lqro_set_user_planes_device.argtypes = [vp, vp, i32, vp]
+        L.lqro_set_fence.argtypes = [vp, vp, vp, dbl]
         L.lqro_set_carry_normal.argtypes = [vp, vp]
         L.lqro_get_carry_normal.argtypes = [vp, vp]
         _lib = L
@@ -284,6 +288,49 @@ class Context:
         AGT:74-81,153-174).  Changes results; max_neighbors <= 0 = all pairs."""
         _check(lib().lqro_set_neighbors(self._h, float(neighbor_dist), int(max_neighbors)),
                "lqro_set_neighbors")
+
+    def set_user_planes(self, plane_lists):
+        """Opt-in half-planes of each agent's LP ahead of its pair planes
+        (lqro_set_user_planes; RVO2's obstacle-first order, AGT:84-151).
+        plane_lists: one (m_i, 6) float32 array per agent (point, normal; v is
+        allowed when normal.(v - point) >= 0), in push order, indexed by the
+        global agent id; None clears.  Changes results against the reference."""
+        if plane_lists is None:
+            _check(lib().lqro_set_user_planes(self._h, None, None), "lqro_set_user_planes")
+            return
+        n = self.cfg.n_agents
+        if len(plane_lists) != n:
+            raise LqroError(f"set_user_planes: {len(plane_lists)} lists for {n} agents")
+        offs = np.zeros(n + 1, dtype=np.int64)
+        for r, p in enumerate(plane_lists):
+            offs[r + 1] = offs[r] + len(p)
+        flat = np.zeros((max(int(offs[-1]), 1), 6), dtype=np.float32)
+        for r, p in enumerate(plane_lists):
+            if len(p):
+                flat[offs[r]:offs[r + 1]] = np.asarray(p, dtype=np.float32).reshape(-1, 6)
+        _check(lib().lqro_set_user_planes(self._h, _p(flat), _p(offs)), "lqro_set_user_planes")
+
+    def set_user_planes_device(self, ptr: int, max_per_agent: int, counts_ptr: int = 0):
+        """The same from device memory at a fixed pitch (e.g. a float32 torch
+        tensor (N, max_per_agent, 6) and an int32 (N,) tensor of live counts,
+        by .data_ptr(); counts_ptr = 0: all live).  The pointers are read when
+        the step's LP runs: keep the tensors alive and write them on the
+        step's stream before the step.  max_per_agent <= 0 clears."""
+        _check(lib().lqro_set_user_planes_device(self._h, C.c_void_p(ptr or None), int(max_per_agent),
+                                                 C.c_void_p(counts_ptr or None)), "lqro_set_user_planes_device")
+
+    def set_fence(self, lo, hi, tau: float):
+        """An axis-aligned box [lo, hi] the agents' ellipsoids should stay
+        inside within tau seconds, as up to six half-planes per agent ahead of
+        the user and pair planes (lqro_set_fence).  -inf / +inf bounds emit no
+        face (lo = (-inf, -inf, 0), hi = inf: a floor); lo = None or tau <= 0
+        turns the fence off.  Changes results against the reference."""
+        if lo is None or hi is None:
+            _check(lib().lqro_set_fence(self._h, None, None, 0.0), "lqro_set_fence")
+            return
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (3,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (3,)))
+        _check(lib().lqro_set_fence(self._h, _p(lo), _p(hi), float(tau)), "lqro_set_fence")
 
     def set_gains(self, A, B, L, E, per_agent: bool = False):
         A, B, L, E = (np.ascontiguousarray(v, dtype=np.float64) for v in (A, B, L, E))
@@ -590,7 +637,8 @@ class Simulator:
     once, then ``step()`` each control step fills every ``Quadrotor.newV``."""
 
     def __init__(self, qlist, horizon: int = 45, n_points: int = 100, device: int = 0,
-                 records: bool = False, model: Model | None = None, hull_rule: str = "reference"):
+                 records: bool = False, model: Model | None = None, hull_rule: str = "reference",
+                 fence=None):
         self.qlist = list(qlist)
         self.model = model or default_model()
         # hull_rule "reference": the reference's own inside-hull rule (Qhull's
@@ -603,6 +651,8 @@ class Simulator:
         self.trajectory = []       # keyframes per step (update())
         self.ctx = Context(config(len(self.qlist), horizon, n_points, device=device,
                                   flags=flags))
+        if fence is not None:      # (lo, hi, tau): Context.set_fence
+            self.ctx.set_fence(*fence)
         self.A = self.B = self.c = None
 
     def findMatrices(self):
@@ -623,7 +673,14 @@ class Simulator:
     def step(self):
         x = np.stack([q.x for q in self.qlist])
         vg = np.stack([q.vGoal for q in self.qlist])
-        newv = self.ctx.step(x, vg)
+        try:
+            newv = self.ctx.step(x, vg)
+        except (QhullMergeSuspect, HullFailure) as e:
+            # the step completed and wrote newV: stored, then raised (as
+            # lqro::Simulator::step does)
+            for q, v in zip(self.qlist, e.newv):
+                q.newV = v.copy()
+            raise
         for q, v in zip(self.qlist, newv):
             q.newV = v.copy()
         return newv
@@ -772,7 +829,7 @@ class DeviceLoop:
     def __init__(self, x0, vgoal0, gains: dict, horizon: int, n_points: int = 100, *,
                  p_goal=None, rank: int = 0, world: int = 1, dist=None, device=None,
                  model: Model | None = None, seed: int = 1, stream=None, rows: str = "block",
-                 flags: int = LQRO_FLAG_QHULL_ORDER):
+                 flags: int = LQRO_FLAG_QHULL_ORDER, fence=None, user_planes=None):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -791,6 +848,12 @@ class DeviceLoop:
         self.ids_h = ids
         self.ids = torch.from_numpy(ids.astype(np.int64)).to(self.dev)
         self.ctx.set_gains(gains["A"], gains["B"], gains["L"], gains["E"])
+        # opt-in constraints ahead of the pair planes: fence = (lo, hi, tau),
+        # user_planes = one (m_i, 6) array per agent (global ids: every rank the same)
+        if fence is not None:
+            self.ctx.set_fence(*fence)
+        if user_planes is not None:
+            self.ctx.set_user_planes(user_planes)
         self.x = torch.from_numpy(np.ascontiguousarray(x0, np.float64)).to(self.dev)
         self.vgoal = torch.from_numpy(np.ascontiguousarray(vgoal0, np.float64)).to(self.dev)
         self.newv = torch.zeros((n, 3), **f64)
