@@ -1,13 +1,77 @@
 // lqro_kern.hpp — launch functions of the kernels compiled in their own
-// objects (lqro_kern_hull.hip, lqro_kern_synth.hip, lqro_kern_dyn.hip), so
-// that liblqro.so's large kernels compile in parallel.
+// objects (lqro_kern_hull.hip, lqro_kern_lp.hip, lqro_kern_synth.hip,
+// lqro_kern_dyn.hip), so that liblqro.so's large kernels compile in parallel
+// and a host edit recompiles none of them.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/lqro.h"
 
+// The arguments of the LP kernels (k_lp, k_lp_lds, k_lp4) and of k_fence.
+// Both stay outside the namespace: they are part of the kernels' names.
+struct LpArgs {
+  int npr, nrows, row_begin, row_stride;
+  // a row's plane list holds at most cap = npr + nfence + umax planes; npr
+  // stays the number of pair slots to compact (no extras: cap == npr)
+  int cap;
+  double vmax;
+  const float* slots;   // per row npr x 8 (flag in [6]: 1 = plane)
+  float* compact;       // per row cap x 8: the row's planes in push order
+  float* proj;          // per row cap x 8: linearProgram4's projected planes
+  // the planes ahead of the pair planes (RVO2's obstacle-first order,
+  // AGT:84-151): k_fence's, per own row nfence x 6 floats, then the user's,
+  // per agent (global id) umax x 6 floats of which ucounts[i] are live
+  // (null: all)
+  const float* fence;
+  const float* uplanes;
+  const int* ucounts;
+  int nfence, umax;
+  const double* vgoal;
+  double* newv;
+  unsigned long long* prof;   // LQRO_LP_PROFILE: cycles per row
+  // rows whose linearProgram3 fails go to k_lp4 (null: linearProgram4 inline)
+  int* lp4_list;              // 6 ints per row: lrow, fail, m, nv.xyz (float bits)
+  int* lp4_count;
+  int* lp4_next;
+  // early LP (lqro_hull.hpp hull_row_done): mode 1 runs the rows whose
+  // count reached row_target and that it claims; mode 2 (the tail) skips the
+  // rows claimed earlier.  rowclaim null: every row.
+  const int* rowpend;
+  int* rowclaim;
+  int row_target;
+  int mode;
+};
+
+// The fence (lqro_set_fence): an axis-aligned box [lo, hi] the agents'
+// ellipsoids (semi-axes m) should stay inside, as at most six half-planes per
+// own row in absolute velocity space, ahead of the user and pair planes
+// (RVO2 puts its obstacle lines first in the same LP, AGT:84-151).  Axis x,
+// y, z, lower face then upper; a face at infinity is not emitted (`faces`).
+// The bound is fp64 in the order written, rounded once.
+struct FenceArgs {
+  int nrows, row_begin, row_stride, X, nfence, faces;
+  double lo[3], hi[3], m[3], tau;
+  const double* x;
+  float* out;
+};
+
 namespace lqro {
 struct HullArgs;
+// k_tables: one workgroup per agent with gains of its own (n_gains: 1 or N)
+void launch_tables(hipStream_t s, int n_gains, int X, int U, int H, const double* A, const double* B, const double* L,
+                   const double* E, int per_agent, double* T, double* NCF, double* R, double* TF, double rad0,
+                   double rad1, double rad2, double umax, int* err);
+constexpr size_t kLpLdsMax = 160 * 1024;   // one CU's LDS: the longest plane list k_lp_lds holds
+// the LP of every row: k_lp_lds (+ k_lp4 for the rows it lists) or, past
+// kLpLdsMax, k_lp.  La.lp4_count / lp4_next must be zero (or lp4_list null).
+// early (La.mode 1, no lp4_list; plan_step: La.cap fits): k_lp_lds at 32 B a
+// plane whatever the length, of which it runs the rows it claims
+hipError_t launch_lp(LpArgs La, hipStream_t s, bool early = false);
+// k_copy_claimed: the rows the early LP ran (claim 1), from src into dst
+void launch_copy_claimed(hipStream_t s, const int* rowclaim, int nrows, int row_begin, int row_stride,
+                         const double* src, double* dst);
+// k_fence: this step's fence planes of every own row
+void launch_fence(hipStream_t s, const FenceArgs& F);
 // k_hull: grid x 8 waves, topology in LDS
 void launch_hull(dim3 grid, hipStream_t s, const HullArgs& A);
 // k_hull_big: one inserting wave, topology in global memory

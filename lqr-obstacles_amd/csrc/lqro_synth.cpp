@@ -1,7 +1,7 @@
 // lqro_synth.cpp — setup-time host helpers of liblqro.so: the model defaults
 // (setup(), LQRObstacles.cpp:169-189, 1275-1286, 559-561) and createSpheres
 // (:735-750), and the reference's noise stream (normal(), :334-350).  The gain synthesis itself (controlMatrices) is shared by the
-// host and the device: lqro_synth.hpp, entry points in lqro_runtime.hip.
+// host and the device: lqro_synth.hpp, entry points in lqro_oneshot.hip.
 #include <cmath>
 
 #include "../../include/lqro.h"

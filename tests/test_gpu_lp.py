@@ -66,7 +66,7 @@ def test_lp_edge_families(lqro_mod, lp_edges):
     _assert_rows_equal(got, e["newv"], "lp_edges.npz", e["cases"], e["names"])
 
 
-# launch_lp (lqro_runtime.hip) picks the plane layout from the longest row:
+# launch_lp (lqro_kern_lp.hip) picks the plane layout from the longest row:
 # 32 B a plane in LDS while npr * 32 <= 64 KiB; then 24 B a plane while
 # npr * 24 <= 160 KiB (linearProgram4's projections in LDS too while both
 # fit: 2 * npr * 24 <= 160 KiB); beyond, everything in global memory
