@@ -1,6 +1,8 @@
-// lqro_kern_hull.hip — the hull kernels (k_hull, k_hull_big; lqro_hull.hpp; k_lhull;
-// lqro_lhull.hpp; k_qhull: lqro_qhull3.hpp; k_qhull_big, k_stale: lqro_qhull.hpp)
-// and their launch functions (lqro_kern.hpp).
+// lqro_kern_hull.hip — the hull kernels (k_hull, k_hull_big: lqro_hull.hpp; k_lhull:
+// lqro_lhull.hpp; k_qhull: lqro_qhull3.hpp, its diagnostics lqro_qhull3_prof.hpp;
+// k_qhull_big, k_stale: lqro_qhull.hpp, with the front end and the commit k_qhull
+// shares; every kernel's job interface: lqro_hull_job.hpp) and their launch
+// functions (lqro_kern.hpp).
 #define LQRO_HULL_TU 1
 #include <hip/hip_runtime.h>
 

@@ -518,16 +518,9 @@ __device__ __forceinline__ void lhull_body(const HullArgs& A, LHullL& L) {
   for (;;) {
     const int slot = hull_take_job(A, L, false);
     if (slot < 0) break;
-    const int lrow = slot / A.npr, jj = A.nbr_list ? A.nbr_list[slot] : slot % A.npr;
-    const int i = A.row_begin + lrow * A.row_stride;
-    const int j = jj < i ? jj : jj + 1;
-    const double* xi = A.x + (size_t)i * A.X;
-    const double* xj = A.x + (size_t)j * A.X;
-    const double* Ti = A.T + (A.per_agent ? (size_t)i * A.H * 9 : 0);
-    const double* Ni = A.NCF + (A.per_agent ? (size_t)i * A.H * 3 * A.X : 0);
-    const double vrel[3] = {xi[3] - xj[3], xi[4] - xj[4], xi[5] - xj[5]};
+    const HullJob J = hull_job(A, slot);
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    const int n = lh_points(A, L, Ti, Ni, xi, xj, vrel, Pr, Pf, C0);
+    const int n = lh_points(A, L, J.Ti, J.Ni, J.xi, J.xj, J.vrel, Pr, Pf, C0);
     const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
     int iters = 0, ncomp = 0;
     unsigned long long tcomp = 0, tset = 0;
@@ -538,7 +531,7 @@ __device__ __forceinline__ void lhull_body(const HullArgs& A, LHullL& L) {
       hl_bar();
     }
     if (!L.fail) {
-      if (tid < 4) lh_face(L, tid, vrel);
+      if (tid < 4) lh_face(L, tid, J.vrel);
       if (tid == 0) { L.nf = 4; L.nv = 4; L.nfree = 0; L.best = INFINITY; L.nc = n; L.cb = 0; L.inlds = 0; }
       hl_bar();
       // a first Q from the support points of LH_DIRS directions (no scans
@@ -551,7 +544,7 @@ __device__ __forceinline__ void lhull_body(const HullArgs& A, LHullL& L) {
         const int q = L.sup[d];
         bool dup = false;
         for (int v = 0; v < L.nv; ++v) dup |= L.vpid[v] == q;
-        if (!dup) lh_insert(L, Pr, q, eps2, band2, vrel);
+        if (!dup) lh_insert(L, Pr, q, eps2, band2, J.vrel);
       }
       if (tid == 0) L.ncompact = L.nv;
       hl_bar();
@@ -584,7 +577,7 @@ __device__ __forceinline__ void lhull_body(const HullArgs& A, LHullL& L) {
             continue;
           const double key = L.bkey[b], nn = L.fn[f][3];
           if (key > 0.0 && key * key > eps2 * nn) {
-            lh_insert(L, Pr, L.bidx[b], eps2, band2, vrel);
+            lh_insert(L, Pr, L.bidx[b], eps2, band2, J.vrel);
           } else if (key > 0.0 || key * key <= band2 * nn) {
             if (tid == 0) L.fail = 22;                   // a point near the facet's plane
             hl_bar();
@@ -594,7 +587,7 @@ __device__ __forceinline__ void lhull_body(const HullArgs& A, LHullL& L) {
           } else {
             if (tid == 0) {
               L.cert[f] = 1;
-              L.best = fmin(L.best, lh_rule(L, f, Pr, Pf, vrel));
+              L.best = fmin(L.best, lh_rule(L, f, Pr, Pf, J.vrel));
             }
             hl_bar();
           }
@@ -605,18 +598,18 @@ __device__ __forceinline__ void lhull_body(const HullArgs& A, LHullL& L) {
     hl_bar();
     const unsigned long long t2 = __builtin_amdgcn_s_memrealtime();
     if (tid == 0 && A.ljobs && L.job < 4096) {
-      unsigned long long* J = A.ljobs + 4 * (size_t)L.job;
-      J[0] = (t1 - t0) | (tset << 32);
-      J[1] = (t2 - t1) | (tcomp << 32);
-      J[2] = (unsigned long long)iters | ((unsigned long long)L.nv << 16) | ((unsigned long long)(L.nc & 0xFFFF) << 32) |
+      unsigned long long* rec = A.ljobs + 4 * (size_t)L.job;
+      rec[0] = (t1 - t0) | (tset << 32);
+      rec[1] = (t2 - t1) | (tcomp << 32);
+      rec[2] = (unsigned long long)iters | ((unsigned long long)L.nv << 16) | ((unsigned long long)(L.nc & 0xFFFF) << 32) |
              ((unsigned long long)gridDim.x << 48);
-      J[3] = (unsigned long long)(n & 0xFFFF) | ((unsigned long long)blockIdx.x << 16) |
+      rec[3] = (unsigned long long)(n & 0xFFFF) | ((unsigned long long)blockIdx.x << 16) |
              ((unsigned long long)L.fail << 32) | ((unsigned long long)L.nf << 40) |
              ((unsigned long long)min(ncomp, 255) << 56);
     }
     if (!L.fail) {
-      hull_select(A, L, L, Pr, Pf, L.vpid, L.nf, [&](int g) { return L.alive[g] && L.cert[g]; }, xi, vrel, slot,
-                  true);
+      hull_select(A, L, L, Pr, Pf, L.vpid, L.nf, [&](int g) { return L.alive[g] && L.cert[g]; }, J.xi,
+                  J.vrel, slot, true);
       if (tid == 0) {
         if (A.recs) A.recs[slot].flags |= LQRO_REC_LOCAL;
         atomicAdd(A.ldone, 1);

@@ -36,7 +36,7 @@
 #pragma once
 #include <float.h>
 
-#include "lqro_hull.hpp"
+#include "lqro_hull_job.hpp"
 #include "lqro_dec16.hpp"
 
 namespace lqro {
@@ -172,16 +172,22 @@ struct QhL {
   int pcnt[QH_NEWCAP + QH_MOVCAP];   // points added this partition
 };
 
+// qh_maxmin's and qh_detroundoff's tolerances of one build and the interior
+// point its planes are oriented by: the same in k_qhull and k_qhull_big
+// (lqro_qh_front.inc sets all but `interior`)
+struct QhTol {
+  double MAXabs_coord, MAXsumcoord, MAXwidth, NEARzero[3];
+  double DISTround, MINvisible, MAXcoplanar, MINoutside, MINdenom, MINdenom_2, max_outside;
+  double interior[3];
+};
+
 // Qhull's scalar state of one build (registers, uniform over the wave)
-struct QhS {
+struct QhS : QhTol {
   int facet_list, facet_tail, facet_next, newfacet_list, visible_list;
   int nins;                     // insertions (qh_addpoint calls), for the build's timing record
   int nalloc, nfree, nv, sbtop, status;
   int nnew, nvis, nmov, nold, epoch;
   int findbestnew, notsharp;
-  double MAXabs_coord, MAXsumcoord, MAXwidth, NEARzero[3];
-  double DISTround, MINvisible, MAXcoplanar, MINoutside, MINdenom, MINdenom_2, max_outside;
-  double interior[3];
   unsigned long long tph[12];   // LQRO_QHULL_PROFILE: cycles per phase
 };
 #ifdef LQRO_QHULL_PROFILE
@@ -249,7 +255,7 @@ __device__ __forceinline__ double qh_dist(const QhW& W, const double* p, int f) 
 #define QH_DET2(a1, a2, b1, b2) ((a1) * (b2) - (a2) * (b1))
 
 // qh_sethyperplane_gauss (dim 3): qh_gausselim + qh_backnormal + qh_normalize2
-__device__ inline void qh_plane_gauss(const QhS& S, int& status, const double* r0, const double* r1,
+__device__ inline void qh_plane_gauss(const QhTol& S, int& status, const double* r0, const double* r1,
                                       const double* r2, int toporient, double* nrm, double* offset) {
   double ra[3] = {r1[0] - r0[0], r1[1] - r0[1], r1[2] - r0[2]};
   double rb[3] = {r2[0] - r0[0], r2[1] - r0[1], r2[2] - r0[2]};
@@ -746,7 +752,7 @@ __device__ inline void qh_extreme(const double* Pr, int n, int k, bool want_max,
   *idx_out = idx;
 }
 
-__device__ inline double qh_detsimplex(const QhS& S, const double* Pr, const int* simplex, int dim, int apex,
+__device__ inline double qh_detsimplex(const QhTol& S, const double* Pr, const int* simplex, int dim, int apex,
                                        int* nearzero) {
   double rows[3][3];
   const double* a = Pr + 3 * (size_t)apex;
@@ -785,90 +791,9 @@ __device__ inline void qh_build(const QhW& W, QhS& S, QhL& L, int n, int lane) {
   W.fnew[0] = 0x7fffffff;
   S.facet_list = S.facet_next = S.newfacet_list = S.visible_list = 0;
   S.nv = 1;
-  // qh_maxmin
-  int maxpoints[6];
-  S.max_outside = 0.0;
-  S.MAXabs_coord = 0.0;
-  S.MAXwidth = -DBL_MAX;
-  S.MAXsumcoord = 0.0;
-  for (int k = 0; k < 3; k++) {
-    int mn, mx;
-    qh_extreme(W.Pr, n, k, false, lane, &mn);
-    qh_extreme(W.Pr, n, k, true, lane, &mx);
-    const double maxk = W.Pr[3 * (size_t)mx + k], mink = W.Pr[3 * (size_t)mn + k];
-    const double maxcoord = fmax(maxk, -mink);
-    const double temp = maxk - mink;
-    if (temp > S.MAXwidth) S.MAXwidth = temp;
-    if (maxcoord > S.MAXabs_coord) S.MAXabs_coord = maxcoord;
-    S.MAXsumcoord += maxcoord;
-    maxpoints[2 * k] = mn;
-    maxpoints[2 * k + 1] = mx;
-    S.NEARzero[k] = 80 * S.MAXsumcoord * DBL_EPSILON;
-  }
-  // qh_detroundoff (C-0)
-  {
-    double maxdistsum = sqrt(3.0) * S.MAXabs_coord;
-    if (S.MAXsumcoord < maxdistsum) maxdistsum = S.MAXsumcoord;
-    S.DISTround = DBL_EPSILON * (3 * maxdistsum * 1.01 + S.MAXabs_coord);
-    const double MINdenom_1 = fmax(1.0 / DBL_MAX, DBL_MIN);
-    S.MINdenom = MINdenom_1 * S.MAXabs_coord;
-    S.MINdenom_2 = sqrt(MINdenom_1 * 3) * S.MAXabs_coord;
-    S.MINvisible = 0.0 + 2 * S.DISTround;
-    S.MAXcoplanar = S.MINvisible;
-    S.MINoutside = 2 * S.MINvisible;
-  }
-  // qh_maxsimplex
-  int simplex[4];
-  {
-    double maxcoord = -DBL_MAX, mincoord = DBL_MAX;
-    int minx = -1, maxx = -1;
-    for (int i = 0; i < 6; i++) {
-      const double c = W.Pr[3 * (size_t)maxpoints[i]];
-      if (maxcoord < c) { maxcoord = c; maxx = maxpoints[i]; }
-      if (mincoord > c) { mincoord = c; minx = maxpoints[i]; }
-    }
-    double maxdet = maxcoord - mincoord;
-    int ns = 0;
-    simplex[ns++] = minx;
-    if (maxx != minx) simplex[ns++] = maxx;
-    if (ns < 2) { S.status |= QHS_INPUT; return; }
-    for (int i = 2; i < 4; i++) {
-      const double prevdet = maxdet;
-      int maxpoint = -1, maxnearzero = 0, nearzero;
-      maxdet = -1.0;
-      for (int m = 0; m < 6; m++) {
-        const int p = maxpoints[m];
-        bool ins = false;
-        for (int t = 0; t < i; t++) ins |= simplex[t] == p;
-        if (!ins && p != maxpoint) {
-          double det = fabs(qh_detsimplex(S, W.Pr, simplex, i, p, &nearzero));
-          if (det > maxdet) { maxdet = det; maxpoint = p; maxnearzero = nearzero; }
-        }
-      }
-      const double targetdet = prevdet * S.MAXwidth;
-      const bool falsenarrow = maxdet > 0.0 && maxdet / targetdet < 1.0e-3;
-      if (maxpoint < 0 || maxnearzero || falsenarrow) {
-        double key = -1.0;
-        int idx = 0x7fffffff;
-        for (int q = lane; q < n; q += 64) {
-          bool skip = false;
-          for (int t = 0; t < 6; t++) skip |= maxpoints[t] == q;
-          for (int t = 0; t < i; t++) skip |= simplex[t] == q;
-          if (skip) continue;
-          const double det = fabs(qh_detsimplex(S, W.Pr, simplex, i, q, &nearzero));
-          if (det > key || (det == key && q < idx)) { key = det; idx = q; }
-        }
-        for (int off = 32; off >= 1; off >>= 1) {
-          const double ok = __shfl_xor(key, off);
-          const int oi = __shfl_xor(idx, off);
-          if (ok > key || (ok == key && oi < idx)) { key = ok; idx = oi; }
-        }
-        if (idx != 0x7fffffff && key > maxdet) { maxdet = key; maxpoint = idx; }
-      }
-      if (maxpoint < 0) { S.status |= QHS_INPUT; return; }
-      simplex[i] = maxpoint;
-    }
-  }
+#define QH_FRONT_FAIL return
+#include "lqro_qh_front.inc"
+#undef QH_FRONT_FAIL
   // qh_initialvertices (v1..v4 = simplex[0..3]; the set is [v4 v3 v2 v1]), qh_createsimplex
   int vset[4];
   for (int i = 0; i < 4; i++) {
@@ -1298,13 +1223,69 @@ __device__ inline bool qh_merge_suspect(const QhW& W, const QhS& S, int lane, co
   return __ballot(sus) != 0;
 }
 
+// Lane 0 commits a selection — the ABI of a Qhull-order hull pair: the plane
+// (or its pending / failed flag), qnrm, the stale queue, the step's counters,
+// the pair's record (bv: the winning facet's point ids, Fv order) and the
+// row's count-down.  bn: the winner's read-back normal, best its distance;
+// returns hull_row_done's result (can_run: the caller runs a closed row's LP).
+__device__ __forceinline__ bool qsel_commit(const HullArgs& A, int slot, const double* xi, bool ok, bool stale,
+                                            bool merged, bool mwin, double best, const double* bn, int nfac,
+                                            int status, const int* bv, bool can_run) {
+  float* pl = A.planes + (size_t)slot * 8;
+  double* qn = A.qnrm + (size_t)slot * 4;
+  double nrm[3] = {0.0, 0.0, 0.0};
+  if (ok && !stale) {
+    nrm[0] = bn[0]; nrm[1] = bn[1]; nrm[2] = bn[2];
+    const double dh = best * 0.5;                      // :1416
+    const double mult = 1.0;                           // :1213
+    pl[0] = (float)(xi[3] + mult * dh * nrm[0]);
+    pl[1] = (float)(xi[4] + mult * dh * nrm[1]);
+    pl[2] = (float)(xi[5] + mult * dh * nrm[2]);
+    pl[3] = (float)nrm[0]; pl[4] = (float)nrm[1]; pl[5] = (float)nrm[2];
+    pl[6] = __int_as_float(1);
+    qn[0] = nrm[0]; qn[1] = nrm[1]; qn[2] = nrm[2]; qn[3] = best;
+    atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
+  } else if (stale) {
+    pl[6] = __int_as_float(3);                         // pending: the loop-carried normal (k_stale)
+    qn[0] = qn[1] = qn[2] = 0.0; qn[3] = best;
+    const int k = atomicAdd(A.qstale_count, 1);
+    if (k < A.qstale_cap) A.qstale[k] = slot;
+    atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
+  } else {
+    pl[6] = __int_as_float(0);
+    hull_fail_note(A.stats, slot);
+  }
+  if (ok && merged) atomicAdd(&A.stats[LQRO_ST_MERGED], 1ull);
+  if (mwin) qhmerge_note(A.stats, slot);
+  if (A.recs) {
+    lqro_pair_record& rec = A.recs[slot];
+    rec.flags |= ok ? LQRO_REC_HULL : LQRO_REC_HULLFAIL;
+    if (stale) rec.flags |= LQRO_REC_STALE;
+    if (merged) rec.flags |= LQRO_REC_QHMERGE;
+    if (mwin) rec.flags |= LQRO_REC_QHMERGE_WIN;
+    rec.n_facets = ok ? nfac : -(status & 0xffff) - 1;   // a failure: -(build status bits) - 1
+    if (ok) {
+      rec.facet[0] = bv[0]; rec.facet[1] = bv[1]; rec.facet[2] = bv[2];
+      rec.dist = best;
+      for (int q = 0; q < 3; ++q) {
+        rec.normal[q] = nrm[q];
+        rec.plane_point[q] = stale ? 0.0f : pl[q];
+        rec.plane_normal[q] = stale ? 0.0f : pl[3 + q];
+      }
+    }
+  }
+  return hull_row_done(A, slot, stale, can_run);
+}
+
 // Facets in Qhull's order, each measured from its first Fv vertex (its
 // newest) with the read-back plane, strict '<': the minimum, the earliest
 // facet in list order on a tie (a walk of the list, only then).  Facet 0 (the
 // list head) winning leaves `normal` to the loop-carried value: the plane
 // waits for k_stale.  Two passes: every facet at full precision for the
 // bound on the minimum, then the read-back planes of the facets within it.
-__device__ inline void qh_select(const HullArgs& A, const QhW& W, const QhS& S, int lane, const double* xi,
+// (out of line, where the compiler left it while qh_body and q3_big_inline
+// each called it: inlined into qh_one_job, k_qhull_big takes 339 VGPRs for 278)
+__device__ inline __noinline__ void qh_select(const HullArgs& A, const QhW& W, const QhS& S, int lane, const double* xi,
                                  const double* vrel, int slot) {
   const bool fail = (S.status & (QHS_INPUT | QHS_TOPOLOGY | QHS_CAPACITY)) != 0;
   double ub = INFINITY;
@@ -1367,52 +1348,11 @@ __device__ inline void qh_select(const HullArgs& A, const QhW& W, const QhS& S, 
   const bool stale = ok && bf == S.facet_list;
   const bool merged = (S.status & (QHS_COPLANAR | QHS_NONCONVEX | QHS_FLIPPED | QHS_NARROW | QHS_SINGULAR)) != 0;
   const bool mwin = ok && merged && qh_merge_suspect(W, S, lane, vrel, best);
-  if (lane == 0) {
-    float* pl = A.planes + (size_t)slot * 8;
-    double* qn = A.qnrm + (size_t)slot * 4;
-    double nrm[3] = {0.0, 0.0, 0.0};
-    if (ok && !stale) {
-      nrm[0] = bn[0]; nrm[1] = bn[1]; nrm[2] = bn[2];
-      const double dh = best * 0.5;                      // :1416
-      const double mult = 1.0;                           // :1213
-      pl[0] = (float)(xi[3] + mult * dh * nrm[0]);
-      pl[1] = (float)(xi[4] + mult * dh * nrm[1]);
-      pl[2] = (float)(xi[5] + mult * dh * nrm[2]);
-      pl[3] = (float)nrm[0]; pl[4] = (float)nrm[1]; pl[5] = (float)nrm[2];
-      pl[6] = __int_as_float(1);
-      qn[0] = nrm[0]; qn[1] = nrm[1]; qn[2] = nrm[2]; qn[3] = best;
-      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
-    } else if (stale) {
-      pl[6] = __int_as_float(3);                         // pending: the loop-carried normal (k_stale)
-      qn[0] = qn[1] = qn[2] = 0.0; qn[3] = best;
-      const int k = atomicAdd(A.qstale_count, 1);
-      if (k < A.qstale_cap) A.qstale[k] = slot;
-      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
-    } else {
-      pl[6] = __int_as_float(0);
-      hull_fail_note(A.stats, slot);
-    }
-    if (ok && merged) atomicAdd(&A.stats[LQRO_ST_MERGED], 1ull);
-    if (mwin) qhmerge_note(A.stats, slot);
-    if (A.recs) {
-      lqro_pair_record& rec = A.recs[slot];
-      rec.flags |= ok ? LQRO_REC_HULL : LQRO_REC_HULLFAIL;
-      if (stale) rec.flags |= LQRO_REC_STALE;
-      if (merged) rec.flags |= LQRO_REC_QHMERGE;
-      if (mwin) rec.flags |= LQRO_REC_QHMERGE_WIN;
-      rec.n_facets = ok ? nfac : -(S.status & 0xffff) - 1;   // a failure: -(build status bits) - 1
-      if (ok) {
-        for (int k = 0; k < 3; k++) rec.facet[k] = W.vpt[W.fv[3 * bf + k]];
-        rec.dist = best;
-        for (int q = 0; q < 3; ++q) {
-          rec.normal[q] = nrm[q];
-          rec.plane_point[q] = stale ? 0.0f : pl[q];
-          rec.plane_normal[q] = stale ? 0.0f : pl[3 + q];
-        }
-      }
-    }
-    hull_row_done(A, slot, stale, false);   // k_qhull_big leaves the LP to the tail
-  }
+  int bv[3] = {0, 0, 0};
+  if (ok)
+    for (int k = 0; k < 3; k++) bv[k] = W.vpt[W.fv[3 * bf + k]];
+  // (k_qhull_big leaves the LP to the tail)
+  if (lane == 0) qsel_commit(A, slot, xi, ok, stale, merged, mwin, best, bn, nfac, S.status, bv, false);
   hl_sync();
 }
 
@@ -1425,6 +1365,37 @@ __device__ inline void qh_claim_scratch(const QhW& W, unsigned* owner, int lane)
   if (lane == 0) *owner = QW_OWNER_QH;
 }
 
+// One job of k_qhull_big's code, by the wave that builds (n: hull_points'
+// count, taken by the whole workgroup before): the scratch claimed, the build,
+// the selection and its commit, the build's timing record (kernel 1, from
+// tjob).  Returns the build's final state.
+__device__ __forceinline__ QhS qh_one_job(const HullArgs& A, const QhW& W, QhL& L, const HullJob& J, int n, int slot,
+                                          unsigned long long tjob, int lane) {
+  qh_claim_scratch(W, qw_owner(A.qscratch + (size_t)(A.block_base + blockIdx.x) * A.qstride, A.qstride), lane);
+  QhS S;
+#ifdef LQRO_QHULL_PROFILE
+  for (int k = 0; k < 12; k++) S.tph[k] = 0;
+#endif
+  S.status = 0;
+  S.nalloc = 1;
+  S.nins = 0;
+  S.facet_list = S.facet_tail = 0;
+  if (L.fail || n < 4) S.status = QHS_INPUT;
+  else qh_build(W, S, L, n, lane);
+  hl_sync();
+#ifdef LQRO_QHULL_PROFILE
+  const unsigned long long tq_ = __builtin_amdgcn_s_memtime();
+#endif
+  // (qh_select is out of line: a copy, or the whole job is kept in scratch for J.vrel's sake)
+  const double vrel[3] = {J.vrel[0], J.vrel[1], J.vrel[2]};
+  qh_select(A, W, S, lane, J.xi, vrel, slot);
+  if (lane == 0) hull_build_note(A, slot, 1, tjob, n, S.nins, S.nalloc - 1);
+#ifdef LQRO_QHULL_PROFILE
+  S.tph[10] = __builtin_amdgcn_s_memtime() - tq_;
+#endif
+  return S;
+}
+
 // one inside-hull pair per wave, persistent over the hull queue (k_qhull_big:
 // the retry queue k_qhull's caps fill, or the main queue under LQRO_QHULL_BIG)
 __device__ inline void qh_body(const HullArgs& A, QhL& L, bool retryq) {
@@ -1435,34 +1406,10 @@ __device__ inline void qh_body(const HullArgs& A, QhL& L, bool retryq) {
     const int slot = hull_take_job(A, L, retryq);
     if (slot < 0) break;
     const unsigned long long tjob = __builtin_amdgcn_s_memrealtime();   // (lqro_get_hull_builds)
-    const int lrow = slot / A.npr, jj = A.nbr_list ? A.nbr_list[slot] : slot % A.npr;
-    const int i = A.row_begin + lrow * A.row_stride;
-    const int j = jj < i ? jj : jj + 1;
-    const double* xi = A.x + (size_t)i * A.X;
-    const double* xj = A.x + (size_t)j * A.X;
-    const double* Ti = A.T + (A.per_agent ? (size_t)i * A.H * 9 : 0);
-    const double* Ni = A.NCF + (A.per_agent ? (size_t)i * A.H * 3 * A.X : 0);
-    const double vrel[3] = {xi[3] - xj[3], xi[4] - xj[4], xi[5] - xj[5]};
-    const int n = hull_points(A, L, Ti, Ni, xi, xj, vrel, W.Pr, W.Pf);
-    qh_claim_scratch(W, qw_owner(A.qscratch + (size_t)(A.block_base + blockIdx.x) * A.qstride, A.qstride), lane);
-    QhS S;
+    const HullJob J = hull_job(A, slot);
+    const int n = hull_points(A, L, J.Ti, J.Ni, J.xi, J.xj, J.vrel, W.Pr, W.Pf);
+    QhS S = qh_one_job(A, W, L, J, n, slot, tjob, lane);
 #ifdef LQRO_QHULL_PROFILE
-    for (int k = 0; k < 12; k++) S.tph[k] = 0;
-#endif
-    S.status = 0;
-    S.nalloc = 1;
-    S.nins = 0;
-    S.facet_list = S.facet_tail = 0;
-    if (L.fail || n < 4) S.status = QHS_INPUT;
-    else qh_build(W, S, L, n, lane);
-    hl_sync();
-#ifdef LQRO_QHULL_PROFILE
-    unsigned long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
-    qh_select(A, W, S, lane, xi, vrel, slot);
-    if (lane == 0) hull_build_note(A, slot, 1, tjob, n, S.nins, S.nalloc - 1);
-#ifdef LQRO_QHULL_PROFILE
-    S.tph[10] = __builtin_amdgcn_s_memtime() - tq_;
     S.tph[11] = 1;
     if (A.prof && lane == 0)
       for (int k = 0; k < 12; k++) atomicAdd(&A.prof[k], S.tph[k]);

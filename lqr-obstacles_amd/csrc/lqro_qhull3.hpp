@@ -31,6 +31,7 @@
 //    as soon as its result is final.
 #pragma once
 #include "lqro_qhull.hpp"
+#include "lqro_qhull3_prof.hpp"
 #include "lqro_lp.hpp"
 
 namespace lqro {
@@ -61,12 +62,6 @@ namespace lqro {
 #endif
 #ifndef Q3_FL
 #define Q3_FL 2240        // facet slots with their hot fields in LDS (the rest of 160 KB)
-#endif
-#define Q3_PROF_RETRY (LQRO_PROF_PAIR + 16)   // profile words: builds handed to k_qhull_big (16)
-#ifdef LQRO_QHULL_PROFILE
-#define Q3_CAPBIT(b) (b)   // which cap sent a build to k_qhull_big (scripts/qhull_prof.py)
-#else
-#define Q3_CAPBIT(b) 0
 #endif
 
 struct Q3G {              // a facet slot >= Q3_FL, 64 B
@@ -261,7 +256,7 @@ struct Q3L {
 };
 static_assert(sizeof(Q3L) <= 160 * 1024, "k_qhull's LDS exceeds a CU");
 
-struct Q3S {
+struct Q3S : QhTol {
   int nalloc, nfs, sbtop, status, qhead, qtail;
   int nins;               // insertions (qh_addpoint calls), for the build's timing record
   unsigned keyc;
@@ -270,74 +265,8 @@ struct Q3S {
   int findbestnew, notsharp;
   int hgen;               // q3_locate_seq's posts to the helper waves (hctl's generation)
   int egen;               // q3_emit_seq's posts (ectl's generation)
-  double MAXabs_coord, MAXsumcoord, MAXwidth, NEARzero[3];
-  double DISTround, MINvisible, MAXcoplanar, MINoutside, MINdenom, MINdenom_2, max_outside;
-  double interior[3];
-  unsigned long long tph[32];   // LQRO_QHULL_PROFILE: phase cycles 0..20, counters 21..28
-  unsigned long long tq;         // LQRO_QHULL_PROFILE: the last stamp
-  unsigned long long tw, nw;     // LQRO_QHULL_PROFILE: waiting for wave 1's speculation
-  unsigned long long tdl;        // LQRO_QHULL_PROFILE: its end until wave 0 sees it
-  unsigned long long tw1, nw1;   // LQRO_QHULL_PROFILE: the waits after one-chunk insertions
-  unsigned long long tse, tsn;   // LQRO_QHULL_PROFILE: publication -> speculation end, -> wave 0 past the wait
-  unsigned long long tfr, nsp;   // LQRO_QHULL_PROFILE: the wait's first read, its spins
-  unsigned long long tfr2, trel;
-  unsigned long long r_start, r_done, r_seen, r_gseen;
-  unsigned long long tseen, tpre, npre, tstart;
-  int prev1;
-  unsigned long long tps[24], nps;   // LQRO_QHULL_PROFILE: phases of the one-chunk insertions
-  unsigned long long lp_n, lp_pts, lp_t, lp_all, lp_tloc, lp_wait, lp_adopt, lp_tail, lp_tw;   // LQRO_QHULL_LONGPROF
-  unsigned long long lp_own, lp_got, lp_hwait, lp_stop, lp_ev, lp_posts;
+  Q3Prof pf;              // the diagnostic builds' words (lqro_qhull3_prof.hpp)
 };
-
-#if defined(LQRO_QHULL_PROFILE) && defined(LQRO_QHULL_PROF_LIGHT)
-// (light: no drain — a phase is charged the waits the build itself makes
-// there, so the phases add up to the undisturbed critical path)
-#define Q3T(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); S.tph[k] += t_ - S.tq; S.tq = t_; } while (0)
-#elif defined(LQRO_QHULL_PROFILE)
-// (every outstanding load and store drained first: a phase is charged its own memory waits)
-#define Q3T(k) do { __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); S.tph[k] += t_ - S.tq; S.tq = t_; } while (0)
-#else
-#define Q3T(k) do {} while (0)
-#endif
-// LQRO_QHULL_PROFILE counters: 21 insertions, 22 partitioned points, 23 located
-// chunks, 24 sequence events, 25 emitted destination groups, 31 adopted speculations
-// Wave 1's own phases and wave 0's wait for it (LQRO_QHULL_PROFILE): prof words
-// Q3_PROF_W1 + k: 0 speculation total, 1 the adopted cone's vertex records,
-// 2 queue scan, 3 horizon, 4 cone, 5 match / checkzero / sharp, 6 serving
-// chunks, 7 speculations, 8 chunks served, 9 wave 0 waiting for a speculation,
-// 10 waits; 16 + k: wave 0's phase k (Q3T) over the insertions whose partition
-// sequence fits one chunk (np <= 64), 40 their number; cycles summed over the
-// step's hulls (lqro_debug_prof_words)
-#define Q3_PROF_W1 LQRO_PROF_QW1
-// LQRO_QHULL_LONGPROF (a diagnostic build, scripts/build_variant.sh): per
-// build record k (lqro_get_hull_builds order, k < 1024), prof words
-// Q3_PROF_LONG + 24 k: insertions whose partition sequence is longer than one
-// chunk, their points, their ticks (100 MHz, from the publication to the end
-// of the emit), the ticks of all the build's partitions, the long ones' ticks
-// to the end of their locate; wave 0's ticks waiting for the speculation,
-// from the wait to the publication, from the emit's end to the next wait;
-// chunks of helped sequences wave 0 located, chunks the helpers did, ticks
-// waiting for them, ticks stopping them, events, posts; helper chunks and
-// their ticks; wave 1's speculations, publication -> seen and seen -> done
-// ticks; wave 0's waits and their speculation-end -> seen ticks
-#define Q3_PROF_LONG LQRO_PROF_QLONG
-struct Q3P {
-  unsigned long long tq2 = 0;   // LQRO_QHULL_PROFILE: the last speculation's end (this wave's clock)
-  unsigned long long t[16];
-  unsigned long long tq;
-};
-#if defined(LQRO_QHULL_PROFILE) && defined(LQRO_QHULL_PROF_LIGHT)
-#define W1T(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); P.t[k] += t_ - P.tq; P.tq = t_; } while (0)
-#elif defined(LQRO_QHULL_PROFILE)
-#define W1T(k) do { __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); P.t[k] += t_ - P.tq; P.tq = t_; } while (0)
-#else
-#define W1T(k) do {} while (0)
-#endif
-#ifdef LQRO_QHULL_PROFILE
-#define Q3C(k, v) do { S.tph[k] += (unsigned long long)(v); } while (0)
-#else
-#define Q3C(k, v) do {} while (0)
-#endif
 
 // ---- facet fields: LDS below Q3_FL, the global record beyond ----
 // Every access names its address space: with two generic pointers the
@@ -487,16 +416,6 @@ __device__ __forceinline__ void q3_set_facet(const Q3W& W, Q3L& L, int f, const 
   }
 }
 
-// the adapter that lets the verified plane code (qh_plane_gauss, qh_detsimplex) read Q3S
-__device__ __forceinline__ QhS q3_as_qhs(const Q3S& S) {
-  QhS T;
-  T.DISTround = S.DISTround;
-  T.MINdenom = S.MINdenom;
-  T.MINdenom_2 = S.MINdenom_2;
-  for (int k = 0; k < 3; k++) T.NEARzero[k] = S.NEARzero[k];
-  return T;
-}
-
 // qh_setfacetplane (qh_sethyperplane_det, nearly singular -> _gauss) for a
 // facet with vertex points r0, r1, r2 in its vertex order; qh_checkflipped
 __device__ inline void q3_plane(const Q3S& S, int& status, const double* r0, const double* r1, const double* r2,
@@ -519,10 +438,8 @@ __device__ inline void q3_plane(const Q3S& S, int& status, const double* r0, con
   double off = -(r0[0] * n[0] + r0[1] * n[1] + r0[2] * n[2]);
   const double d2 = off + (r2[0] * n[0] + r2[1] * n[1] + r2[2] * n[2]);
   const double d1 = off + (r1[0] * n[0] + r1[1] * n[1] + r1[2] * n[2]);
-  if (d2 > S.DISTround || d2 < -S.DISTround || d1 > S.DISTround || d1 < -S.DISTround) {
-    const QhS T = q3_as_qhs(S);
-    qh_plane_gauss(T, status, r0, r1, r2, top, n, &off);
-  }
+  if (d2 > S.DISTround || d2 < -S.DISTround || d1 > S.DISTround || d1 < -S.DISTround)
+    qh_plane_gauss(S, status, r0, r1, r2, top, n, &off);
   q[0] = n[0]; q[1] = n[1]; q[2] = n[2]; q[3] = off;
   const double di = off + S.interior[0] * n[0] + S.interior[1] * n[1] + S.interior[2] * n[2];
   *flipped = di >= -S.DISTround;
@@ -1034,11 +951,11 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
 #endif
           if (!mine) st = q3_wait(&L.hr_st[b], k + 1, false);
 #ifdef LQRO_QHULL_LONGPROF
-          if (!mine) S.lp_hwait += __builtin_amdgcn_s_memrealtime() - tw0;
+          if (!mine) S.pf.lp_hwait += __builtin_amdgcn_s_memrealtime() - tw0;
 #endif
         }
 #ifdef LQRO_QHULL_LONGPROF
-        if (mine) S.lp_own++; else S.lp_got++;
+        if (mine) S.pf.lp_own++; else S.pf.lp_got++;
 #endif
         int kv = 0;
         if (!mine) {
@@ -1120,7 +1037,11 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
 #endif
     if (help) stop();   // (the rest, if any, is posted again under the new state)
 #ifdef LQRO_QHULL_LONGPROF
-    if (help) { S.lp_stop += __builtin_amdgcn_s_memrealtime() - ts0; S.lp_posts++; if (ev_pos < np) S.lp_ev++; }
+    if (help) {
+      S.pf.lp_stop += __builtin_amdgcn_s_memrealtime() - ts0;
+      S.pf.lp_posts++;
+      if (ev_pos < np) S.pf.lp_ev++;
+    }
 #endif
     if (S.status & QHS_CAPACITY) return;
     if (ev_pos < np) {
@@ -2051,7 +1972,7 @@ __device__ inline void q3_prefetch(const Q3W& W, Q3L& L, int lane, int p) {
 // for step)
 __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
 #ifdef LQRO_QHULL_PROFILE
-  S.tq = __builtin_amdgcn_s_memtime();
+  S.pf.tq = __builtin_amdgcn_s_memtime();
 #endif
   const unsigned long long ltmask = (1ull << lane) - 1ull;
   S.status = 0;
@@ -2069,91 +1990,9 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
     S.status |= QHS_CAPACITY | Q3_CAPBIT(QHS_CAP_FACETS);
     return;
   }
-  // qh_maxmin
-  int maxpoints[6];
-  S.max_outside = 0.0;
-  S.MAXabs_coord = 0.0;
-  S.MAXwidth = -DBL_MAX;
-  S.MAXsumcoord = 0.0;
-  for (int k = 0; k < 3; k++) {
-    int mn, mx;
-    qh_extreme(W.Pr, n, k, false, lane, &mn);
-    qh_extreme(W.Pr, n, k, true, lane, &mx);
-    const double maxk = W.Pr[3 * (size_t)mx + k], mink = W.Pr[3 * (size_t)mn + k];
-    const double maxcoord = fmax(maxk, -mink);
-    const double temp = maxk - mink;
-    if (temp > S.MAXwidth) S.MAXwidth = temp;
-    if (maxcoord > S.MAXabs_coord) S.MAXabs_coord = maxcoord;
-    S.MAXsumcoord += maxcoord;
-    maxpoints[2 * k] = mn;
-    maxpoints[2 * k + 1] = mx;
-    S.NEARzero[k] = 80 * S.MAXsumcoord * DBL_EPSILON;
-  }
-  // qh_detroundoff (C-0)
-  {
-    double maxdistsum = sqrt(3.0) * S.MAXabs_coord;
-    if (S.MAXsumcoord < maxdistsum) maxdistsum = S.MAXsumcoord;
-    S.DISTround = DBL_EPSILON * (3 * maxdistsum * 1.01 + S.MAXabs_coord);
-    const double MINdenom_1 = fmax(1.0 / DBL_MAX, DBL_MIN);
-    S.MINdenom = MINdenom_1 * S.MAXabs_coord;
-    S.MINdenom_2 = sqrt(MINdenom_1 * 3) * S.MAXabs_coord;
-    S.MINvisible = 0.0 + 2 * S.DISTround;
-    S.MAXcoplanar = S.MINvisible;
-    S.MINoutside = 2 * S.MINvisible;
-  }
-  // qh_maxsimplex
-  int simplex[4];
-  {
-    const QhS T = q3_as_qhs(S);
-    double maxcoord = -DBL_MAX, mincoord = DBL_MAX;
-    int minx = -1, maxx = -1;
-    for (int i = 0; i < 6; i++) {
-      const double c = W.Pr[3 * (size_t)maxpoints[i]];
-      if (maxcoord < c) { maxcoord = c; maxx = maxpoints[i]; }
-      if (mincoord > c) { mincoord = c; minx = maxpoints[i]; }
-    }
-    double maxdet = maxcoord - mincoord;
-    int ns = 0;
-    simplex[ns++] = minx;
-    if (maxx != minx) simplex[ns++] = maxx;
-    if (ns < 2) { S.status |= QHS_INPUT; return; }
-    for (int i = 2; i < 4; i++) {
-      const double prevdet = maxdet;
-      int maxpoint = -1, maxnearzero = 0, nearzero;
-      maxdet = -1.0;
-      for (int m = 0; m < 6; m++) {
-        const int p = maxpoints[m];
-        bool ins = false;
-        for (int t = 0; t < i; t++) ins |= simplex[t] == p;
-        if (!ins && p != maxpoint) {
-          const double det = fabs(qh_detsimplex(T, W.Pr, simplex, i, p, &nearzero));
-          if (det > maxdet) { maxdet = det; maxpoint = p; maxnearzero = nearzero; }
-        }
-      }
-      const double targetdet = prevdet * S.MAXwidth;
-      const bool falsenarrow = maxdet > 0.0 && maxdet / targetdet < 1.0e-3;
-      if (maxpoint < 0 || maxnearzero || falsenarrow) {
-        double key = -1.0;
-        int idx = 0x7fffffff;
-        for (int q = lane; q < n; q += 64) {
-          bool skip = false;
-          for (int t = 0; t < 6; t++) skip |= maxpoints[t] == q;
-          for (int t = 0; t < i; t++) skip |= simplex[t] == q;
-          if (skip) continue;
-          const double det = fabs(qh_detsimplex(T, W.Pr, simplex, i, q, &nearzero));
-          if (det > key || (det == key && q < idx)) { key = det; idx = q; }
-        }
-        for (int off = 32; off >= 1; off >>= 1) {
-          const double ok = __shfl_xor(key, off);
-          const int oi = __shfl_xor(idx, off);
-          if (ok > key || (ok == key && oi < idx)) { key = ok; idx = oi; }
-        }
-        if (idx != 0x7fffffff && key > maxdet) { maxdet = key; maxpoint = idx; }
-      }
-      if (maxpoint < 0) { S.status |= QHS_INPUT; return; }
-      simplex[i] = maxpoint;
-    }
-  }
+#define QH_FRONT_FAIL return
+#include "lqro_qh_front.inc"
+#undef QH_FRONT_FAIL
   // qh_initialvertices (the vertex set is [v4 v3 v2 v1], v_k = simplex[k-1]),
   // qh_createsimplex: facet slots 1..4, keys 1..4, facet i without vertex i
   const int pset[4] = {simplex[3], simplex[2], simplex[1], simplex[0]};
@@ -2377,7 +2216,7 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
   for (;;) {
 #ifdef LQRO_QHULL_PROFILE
     unsigned long long snap_[21];
-    for (int k = 0; k < 21; k++) snap_[k] = S.tph[k];
+    for (int k = 0; k < 21; k++) snap_[k] = S.pf.tph[k];
 #endif
     // qh_nextfurthest: the first queued facet still alive (same key) with
     // points
@@ -2397,7 +2236,7 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
     int pfa = 0, pfnp = -1;
 #ifdef LQRO_QHULL_LONGPROF
     const unsigned long long lp_ta = __builtin_amdgcn_s_memrealtime();
-    S.lp_tail += S.lp_tw ? lp_ta - S.lp_tw : 0ull;
+    S.pf.lp_tail += S.pf.lp_tw ? lp_ta - S.pf.lp_tw : 0ull;
 #endif
     if (phase > 0) {
 #ifdef LQRO_QHULL_PROFILE
@@ -2412,7 +2251,7 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
         dn = q3_ld_acq(&L.sp_done);
         ++spins_;
       }
-      if (S.prev1) { S.tfr += tf_ - tw_; S.nsp += (unsigned long long)spins_; }
+      if (S.pf.prev1) { S.pf.tfr += tf_ - tw_; S.pf.nsp += (unsigned long long)spins_; }
 #else
       const int dn = q3_wait(&L.sp_done, phase, false);
 #endif
@@ -2426,21 +2265,21 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
 #ifdef LQRO_QHULL_PROFILE
       {
         const unsigned long long tn_ = __builtin_amdgcn_s_memtime();
-        S.tw += tn_ - tw_;
-        S.nw += 1;
-        if (tn_ - tw_ > 200) S.tdl += tn_ - L.done_t;   // (waited) speculation end -> seen here
-        S.tseen = tn_;
-        if (S.prev1) {   // after a one-chunk insertion: its wait, publication -> speculation end / -> seen
-          S.tw1 += tn_ - tw_; S.nw1 += 1;
-          S.tse += L.done_t - L.pub_t; S.tsn += tn_ - L.pub_t;
-          S.tfr2 += L.done_t2 - L.pub_t;
+        S.pf.tw += tn_ - tw_;
+        S.pf.nw += 1;
+        if (tn_ - tw_ > 200) S.pf.tdl += tn_ - L.done_t;   // (waited) speculation end -> seen here
+        S.pf.tseen = tn_;
+        if (S.pf.prev1) {   // after a one-chunk insertion: its wait, publication -> speculation end / -> seen
+          S.pf.tw1 += tn_ - tw_; S.pf.nw1 += 1;
+          S.pf.tse += L.done_t - L.pub_t; S.pf.tsn += tn_ - L.pub_t;
+          S.pf.tfr2 += L.done_t2 - L.pub_t;
           const unsigned long long nr_ = __builtin_amdgcn_s_memrealtime();
-          S.r_start += L.start_r - L.pub_r; S.r_done += L.done_r - L.pub_r; S.r_seen += nr_ - L.pub_r;
+          S.pf.r_start += L.start_r - L.pub_r; S.pf.r_done += L.done_r - L.pub_r; S.pf.r_seen += nr_ - L.pub_r;
         }
       }
 #endif
 #ifdef LQRO_QHULL_LONGPROF
-      S.lp_wait += __builtin_amdgcn_s_memrealtime() - lp_ta;
+      S.pf.lp_wait += __builtin_amdgcn_s_memrealtime() - lp_ta;
 #endif
       if (dn != phase) {   // wave 1 still speculating (it writes vertex records from L.nslot): stop
         S.status |= QHS_CAPACITY | QHS_TIMEOUT;
@@ -2608,7 +2447,7 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
     }
     Q3T(1);
 #ifdef LQRO_QHULL_PROFILE
-    const unsigned long long tins_ = S.tq;   // this insertion's start (for the long-sequence split)
+    const unsigned long long tins_ = S.pf.tq;   // this insertion's start (for the long-sequence split)
 #endif
     if (furthest < 0) {
       // the build is done: the selection reads vertex records wave 1 wrote
@@ -2934,16 +2773,17 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
     ++phase;
 #ifdef LQRO_QHULL_PROFILE
     if (lane == 0) { L.pub_t = __builtin_amdgcn_s_memtime(); L.pub_r = __builtin_amdgcn_s_memrealtime(); }
-    if (S.tseen) { S.tpre += __builtin_amdgcn_s_memtime() - S.tseen; S.npre += 1; }   // (this wave's clock) seen -> publication
+    // (this wave's clock) seen -> publication
+    if (S.pf.tseen) { S.pf.tpre += __builtin_amdgcn_s_memtime() - S.pf.tseen; S.pf.npre += 1; }
 #endif
 #ifdef LQRO_QHULL_LONGPROF
     const unsigned long long lp_t0 = __builtin_amdgcn_s_memrealtime();
-    S.lp_adopt += lp_t0 - lp_ta;   // (less the wait, in lp_wait)
+    S.pf.lp_adopt += lp_t0 - lp_ta;   // (less the wait, in lp_wait)
     if (lane == 0) L.lp_pubr = lp_t0;
 #endif
     if (lane == 0) q3_st_rel(&L.ph, phase);
 #ifdef LQRO_QHULL_PROFILE
-    if (lane == 0) S.trel += __builtin_amdgcn_s_memtime() - L.pub_t;   // the release's own cost
+    if (lane == 0) S.pf.trel += __builtin_amdgcn_s_memtime() - L.pub_t;   // the release's own cost
 #endif
     S.findbestnew = 0;
     S.notsharp = 0;
@@ -2979,7 +2819,7 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
       HullPt rpt;
       q3_locate_seq(W, S, L, np2, sharp, false, lane, pre, prestart, true, rg, rd, rpt);
 #ifdef LQRO_QHULL_LONGPROF
-      if (np2 > 64) S.lp_tloc += __builtin_amdgcn_s_memrealtime() - lp_t0;
+      if (np2 > 64) S.pf.lp_tloc += __builtin_amdgcn_s_memrealtime() - lp_t0;
 #endif
       Q3T(6);
       q3_emit_seq(W, S, L, np2, nnew, false, lane, rg, rd, rpt);
@@ -2988,9 +2828,9 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
 #ifdef LQRO_QHULL_LONGPROF
     {
       const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - lp_t0;
-      S.lp_all += dt;
-      if (np2 > 64) { S.lp_n += 1; S.lp_pts += (unsigned long long)np2; S.lp_t += dt; }
-      S.lp_tw = lp_t0 + dt;
+      S.pf.lp_all += dt;
+      if (np2 > 64) { S.pf.lp_n += 1; S.pf.lp_pts += (unsigned long long)np2; S.pf.lp_t += dt; }
+      S.pf.lp_tw = lp_t0 + dt;
     }
 #endif
     if (S.status & QHS_CAPACITY) return;
@@ -3038,11 +2878,11 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
     Q3T(9);
 #ifdef LQRO_QHULL_PROFILE
     // insertions whose partition sequence is longer than one chunk: 29 cycles, 30 count
-    S.prev1 = np2 <= 64;
-    if (np2 > 64) { S.tph[29] += S.tq - tins_; S.tph[30] += 1; }
+    S.pf.prev1 = np2 <= 64;
+    if (np2 > 64) { S.pf.tph[29] += S.pf.tq - tins_; S.pf.tph[30] += 1; }
     else {
-      for (int k = 0; k < 21; k++) S.tps[k] += S.tph[k] - snap_[k];
-      S.nps += 1;
+      for (int k = 0; k < 21; k++) S.pf.tps[k] += S.pf.tph[k] - snap_[k];
+      S.pf.nps += 1;
     }
 #endif
   }
@@ -3179,52 +3019,8 @@ __device__ inline bool q3_select(const HullArgs& A, const Q3W& W, const Q3L& L, 
   if (ok)
     for (int t = 0; t < 3; t++) bv[t] = W.vv[bf].id[t];
   int go = 0;
-  if (lane == 0) {
-    float* pl = A.planes + (size_t)slot * 8;
-    double* qn = A.qnrm + (size_t)slot * 4;
-    double nrm[3] = {0.0, 0.0, 0.0};
-    if (ok && !stale) {
-      nrm[0] = bn[0]; nrm[1] = bn[1]; nrm[2] = bn[2];
-      const double dh = best * 0.5;                      // :1416
-      const double mult = 1.0;                           // :1213
-      pl[0] = (float)(xi[3] + mult * dh * nrm[0]);
-      pl[1] = (float)(xi[4] + mult * dh * nrm[1]);
-      pl[2] = (float)(xi[5] + mult * dh * nrm[2]);
-      pl[3] = (float)nrm[0]; pl[4] = (float)nrm[1]; pl[5] = (float)nrm[2];
-      pl[6] = __int_as_float(1);
-      qn[0] = nrm[0]; qn[1] = nrm[1]; qn[2] = nrm[2]; qn[3] = best;
-      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
-    } else if (stale) {
-      pl[6] = __int_as_float(3);                         // pending: the loop-carried normal (k_stale)
-      qn[0] = qn[1] = qn[2] = 0.0; qn[3] = best;
-      const int k = atomicAdd(A.qstale_count, 1);
-      if (k < A.qstale_cap) A.qstale[k] = slot;
-      atomicAdd(&A.stats[LQRO_ST_HULLOK], 1ull);
-    } else {
-      pl[6] = __int_as_float(0);
-      hull_fail_note(A.stats, slot);
-    }
-    if (ok && merged) atomicAdd(&A.stats[LQRO_ST_MERGED], 1ull);
-    if (mwin) qhmerge_note(A.stats, slot);
-    if (A.recs) {
-      lqro_pair_record& rec = A.recs[slot];
-      rec.flags |= ok ? LQRO_REC_HULL : LQRO_REC_HULLFAIL;
-      if (stale) rec.flags |= LQRO_REC_STALE;
-      if (merged) rec.flags |= LQRO_REC_QHMERGE;
-      if (mwin) rec.flags |= LQRO_REC_QHMERGE_WIN;
-      rec.n_facets = ok ? nfac : -(S.status & 0xffff) - 1;
-      if (ok) {
-        rec.facet[0] = bv[0]; rec.facet[1] = bv[1]; rec.facet[2] = bv[2];
-        rec.dist = best;
-        for (int q = 0; q < 3; ++q) {
-          rec.normal[q] = nrm[q];
-          rec.plane_point[q] = stale ? 0.0f : pl[q];
-          rec.plane_normal[q] = stale ? 0.0f : pl[3 + q];
-        }
-      }
-    }
-    go = hull_row_done(A, slot, stale, A.row_lp != 0);
-  }
+  if (lane == 0)
+    go = qsel_commit(A, slot, xi, ok, stale, merged, mwin, best, bn, nfac, S.status, bv, A.row_lp != 0);
   hl_sync();
   return __builtin_amdgcn_readfirstlane(go) != 0;
 }
@@ -3270,32 +3066,9 @@ __device__ inline void q3_big_inline(const HullArgs& A, QhL& LB, int slot, unsig
   const int lane = threadIdx.x & 63;
   const int HNP = A.H * A.NP;
   const QhW W = qh_worker(A.qscratch + (size_t)(A.block_base + blockIdx.x) * A.qstride, HNP);
-  const int lrow = slot / A.npr, jj = A.nbr_list ? A.nbr_list[slot] : slot % A.npr;
-  const int i = A.row_begin + lrow * A.row_stride;
-  const int j = jj < i ? jj : jj + 1;
-  const double* xi = A.x + (size_t)i * A.X;
-  const double* xj = A.x + (size_t)j * A.X;
-  const double* Ti = A.T + (A.per_agent ? (size_t)i * A.H * 9 : 0);
-  const double* Ni = A.NCF + (A.per_agent ? (size_t)i * A.H * 3 * A.X : 0);
-  const double vrel[3] = {xi[3] - xj[3], xi[4] - xj[4], xi[5] - xj[5]};
-  const int n = hull_points(A, LB, Ti, Ni, xi, xj, vrel, W.Pr, W.Pf);
-  unsigned* owner = qw_owner(A.qscratch + (size_t)(A.block_base + blockIdx.x) * A.qstride, A.qstride);
-  if (wave == 0) {
-    qh_claim_scratch(W, owner, lane);
-    QhS S;
-#ifdef LQRO_QHULL_PROFILE
-    for (int k = 0; k < 12; k++) S.tph[k] = 0;
-#endif
-    S.status = 0;
-    S.nalloc = 1;
-    S.nins = 0;
-    S.facet_list = S.facet_tail = 0;
-    if (LB.fail || n < 4) S.status = QHS_INPUT;
-    else qh_build(W, S, LB, n, lane);
-    hl_sync();
-    qh_select(A, W, S, lane, xi, vrel, slot);
-    if (lane == 0) hull_build_note(A, slot, 1, tjob, n, S.nins, S.nalloc - 1);
-  }
+  const HullJob J = hull_job(A, slot);
+  const int n = hull_points(A, LB, J.Ti, J.Ni, J.xi, J.xj, J.vrel, W.Pr, W.Pf);
+  if (wave == 0) qh_one_job(A, W, LB, J, n, slot, tjob, lane);
 }
 
 // one inside-hull pair per wave (one wave per CU), persistent over the hull
@@ -3320,22 +3093,12 @@ __device__ __forceinline__ void q3_body(const HullArgs& A, Q3L& L, QhL* LB = nul
       L.ph = 0; L.sp_done = 0; L.sp_gdone = 0; L.hctl = 0u; L.hbusy = 0; L.sp_hz = 0; L.pf_done = 0;
       L.ectl = 0u; L.edone = 0;
       L.qflags = A.qflags;
-#ifdef LQRO_QHULL_LONGPROF
-      for (int k = 0; k < 12; k++) L.hprof[k] = 0ull;
-      L.lp_pubr = L.lp_doner = 0ull;
-#endif
+      q3_longprof_begin(L);
       L.big_slot = -1;
     }
     for (int q = threadIdx.x; q < Q3_FL / 2; q += blockDim.x) reinterpret_cast<unsigned*>(L.mark)[q] = 0u;
-    const int lrow = slot / A.npr, jj = A.nbr_list ? A.nbr_list[slot] : slot % A.npr;
-    const int i = A.row_begin + lrow * A.row_stride;
-    const int j = jj < i ? jj : jj + 1;
-    const double* xi = A.x + (size_t)i * A.X;
-    const double* xj = A.x + (size_t)j * A.X;
-    const double* Ti = A.T + (A.per_agent ? (size_t)i * A.H * 9 : 0);
-    const double* Ni = A.NCF + (A.per_agent ? (size_t)i * A.H * 3 * A.X : 0);
-    const double vrel[3] = {xi[3] - xj[3], xi[4] - xj[4], xi[5] - xj[5]};
-    const int n = hull_points(A, L, Ti, Ni, xi, xj, vrel, W.Pr, W.Pf);
+    const HullJob J = hull_job(A, slot);
+    const int n = hull_points(A, L, J.Ti, J.Ni, J.xi, J.xj, J.vrel, W.Pr, W.Pf);
     bool lp_go = false;
     if (wave >= 2) {
       // wave 2: prefetch each horizon wave 1 publishes; waves 2 and 3: locate
@@ -3438,34 +3201,14 @@ __device__ __forceinline__ void q3_body(const HullArgs& A, Q3L& L, QhL* LB = nul
         if (++idle > (1l << 24)) break;
         __builtin_amdgcn_s_sleep(Q3_W1_SLEEP);
       }
-#ifdef LQRO_QHULL_PROFILE
-      if (A.prof && lane == 0)
-        for (int k = 0; k < 16; k++) atomicAdd(&A.prof[Q3_PROF_W1 + k], P.t[k]);
-#endif
+      q3_prof_w1_flush(A, P, lane);
       if (lane == 0) W.ctr[0] = ep2;
     } else {
     Q3S S;
-#ifdef LQRO_QHULL_PROFILE
-    for (int k = 0; k < 32; k++) S.tph[k] = 0;
-    S.tw = S.nw = 0;
-    S.tdl = 0;
-    S.tw1 = S.nw1 = 0;
-    S.tse = S.tsn = 0;
-    S.tfr = S.nsp = 0;
-    S.tfr2 = 0;
-    S.trel = 0;
-    S.r_start = S.r_done = S.r_seen = S.r_gseen = 0;
-    S.tseen = S.tpre = S.npre = S.tstart = 0;
-    S.prev1 = 0;
-    for (int k = 0; k < 24; k++) S.tps[k] = 0;
-    S.nps = 0;
-    const unsigned long long tjob_ = __builtin_amdgcn_s_memtime();
-#endif
+    q3_prof_begin(S.pf);
     S.status = 0;
     S.nalloc = 1;
     S.nins = 0;
-    S.lp_n = S.lp_pts = S.lp_t = S.lp_all = S.lp_tloc = S.lp_wait = S.lp_adopt = S.lp_tail = S.lp_tw = 0;
-    S.lp_own = S.lp_got = S.lp_hwait = S.lp_stop = S.lp_ev = S.lp_posts = 0;
     if (L.fail || n < 4) S.status = QHS_INPUT;
     else q3_build(W, S, L, n, lane);
     hl_sync();
@@ -3501,72 +3244,14 @@ __device__ __forceinline__ void q3_body(const HullArgs& A, Q3L& L, QhL* LB = nul
           if (r < A.cap) A.rqueue[r] = slot;
         }
         hull_build_note(A, slot, 2, tjob, n, S.nins, S.nalloc - 1);
-#ifdef LQRO_QHULL_PROFILE
-        // the builds handed to k_qhull_big: count, the caps they hit, slots
-        if (A.prof) {
-          const unsigned long long k = atomicAdd(&A.prof[Q3_PROF_RETRY], 1ull);
-          atomicOr(&A.prof[Q3_PROF_RETRY + 1], (unsigned long long)S.status);
-          if (k < 14) A.prof[Q3_PROF_RETRY + 2 + k] = (unsigned long long)slot | ((unsigned long long)S.status << 32);
-        }
-#endif
+        q3_prof_retry(A, S.status, slot);
       }
       hl_sync();
     } else {
-#ifdef LQRO_QHULL_PROFILE
-    unsigned long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
-    lp_go = q3_select(A, W, L, S, lane, xi, vrel, slot);
-    if (lane == 0) {
-      const int k = hull_build_note(A, slot, 0, tjob, n, S.nins, S.nalloc - 1);
-#ifdef LQRO_QHULL_LONGPROF
-      if (A.prof && k >= 0 && k < 1024) {
-        unsigned long long* r = A.prof + Q3_PROF_LONG + 24 * k;
-        r[0] = S.lp_n; r[1] = S.lp_pts; r[2] = S.lp_t; r[3] = S.lp_all;
-        r[4] = S.lp_tloc; r[5] = S.lp_wait; r[6] = S.lp_adopt - S.lp_wait; r[7] = S.lp_tail;
-        r[8] = S.lp_own; r[9] = S.lp_got; r[10] = S.lp_hwait; r[11] = S.lp_stop; r[12] = S.lp_ev; r[13] = S.lp_posts;
-        r[14] = L.hprof[0]; r[15] = L.hprof[1] | (L.hprof[2] << 32);
-        for (int q = 3; q < 11; q++) r[13 + q] = L.hprof[q];   // r[16..23]
-      }
-#else
-      (void)k;
-#endif
-    }
-#ifdef LQRO_QHULL_PROFILE
-    S.tph[10] = __builtin_amdgcn_s_memtime() - tq_;
-    S.tph[27] = __builtin_amdgcn_s_memtime() - tjob_;   // the whole job (26: its max over jobs)
-    S.tph[28] = (unsigned long long)n;
-    if (A.prof && lane == 0) {
-      for (int k = 0; k < 32; k++)
-        if (k != 26 && k != 11) atomicAdd(&A.prof[k], S.tph[k]);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 9], S.tw);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 10], S.nw);
-      for (int k = 0; k < 24; k++) atomicAdd(&A.prof[Q3_PROF_W1 + 16 + k], S.tps[k]);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 40], S.nps);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 41], S.tdl);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 42], S.tw1);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 43], S.nw1);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 44], S.tse);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 45], S.tsn);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 46], S.tfr);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 47], S.nsp);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 48], S.tfr2);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 49], S.trel);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 50], S.r_start);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 51], S.r_done);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 52], S.r_seen);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 53], S.r_gseen);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 54], S.tpre);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 55], S.npre);
-      atomicAdd(&A.prof[Q3_PROF_W1 + 56], S.tstart);
-      atomicMax(&A.prof[26], S.tph[27]);
-      // per job (words 32 + 2j): cycles; insertions | points << 20 | facet slots << 40
-      const unsigned long long j = atomicAdd(&A.prof[11], 1ull);
-      if (j < 4096) {
-        A.prof[32 + 2 * j] = S.tph[27];
-        A.prof[33 + 2 * j] = S.tph[21] | ((unsigned long long)n << 20) | ((unsigned long long)S.nalloc << 40);
-      }
-    }
-#endif
+    q3_prof_stamp(S.pf);
+    lp_go = q3_select(A, W, L, S, lane, J.xi, J.vrel, slot);
+    if (lane == 0) q3_longprof_flush(A, hull_build_note(A, slot, 0, tjob, n, S.nins, S.nalloc - 1), S.pf, L);
+    q3_prof_flush(A, S.pf, n, S.nalloc, lane);
     if (A.ext_nf && lane == 0) *A.ext_nf = S.status;   // test hook: the build's status bits
     if (A.ext_facets) {                                  // test hook: the facet list in key order
       for (int f = 1 + lane; f < S.nalloc; f += 64) {

@@ -26,9 +26,7 @@ def _golden():
     return np.load(QO)
 
 
-def test_qhull_hook_on_injected_pairs(lqro_mod, oracle, gains):
-    """Qhull's full output for six dense-swarm pairs: k_qhull's build and
-    selection through the test hook equal the oracle's and the golden's."""
+def _hook_on_injected_pairs(lqro_mod, oracle, gains):
     d = _golden()
     ctx = lqro_mod.Context(lqro_mod.config(2, 45, 100))
     ctx.set_gains(gains["A"], gains["B"], gains["L"], gains["E"])
@@ -55,6 +53,19 @@ def test_qhull_hook_on_injected_pairs(lqro_mod, oracle, gains):
     finally:
         oracle.set_hull_rule(0)
         ctx.close()
+
+
+def test_qhull_hook_on_injected_pairs(lqro_mod, oracle, gains):
+    """Qhull's full output for six dense-swarm pairs: k_qhull's build and
+    selection through the test hook equal the oracle's and the golden's."""
+    _hook_on_injected_pairs(lqro_mod, oracle, gains)
+
+
+def test_qhull_hook_on_injected_pairs_big(lqro_mod, oracle, gains, monkeypatch):
+    """The same six pairs through k_qhull_big (LQRO_QHULL_BIG=1, read when the
+    context is created): the fallback's build, selection and commit."""
+    monkeypatch.setenv("LQRO_QHULL_BIG", "1")
+    _hook_on_injected_pairs(lqro_mod, oracle, gains)
 
 
 def test_qhull_hook_on_reference_fixture(lqro_mod, oracle, gains):
@@ -97,13 +108,18 @@ def _ref_step(lqro_mod, oracle, gains, N, H, box, seed, steps=1):
     out = []
     for _ in range(steps):
         v = ctx.step(x, vg)
-        out.append((v, ctx.records(), ctx.stats(), ctx.carry_normal()))
+        out.append((v, ctx.records(), ctx.stats(), ctx.carry_normal(), ctx.hull_builds()))
     ctx.close()
     return x, vg, out
 
 
-@pytest.mark.parametrize("case", ["dense", "c2"])
-def test_qhull_order_step_vs_oracle(lqro_mod, oracle, gains, case):
+@pytest.mark.parametrize("case,big", [("dense", 0), ("c2", 0), ("dense", 1)], ids=["dense", "c2", "dense-big"])
+def test_qhull_order_step_vs_oracle(lqro_mod, oracle, gains, monkeypatch, case, big):
+    """big = 1: every pair through k_qhull_big (LQRO_QHULL_BIG=1, read when the
+    context is created), on the dense swarm: its inside-hull pairs take both
+    the plane branch and the stale branch (facet 0 wins) of the commit."""
+    if big:
+        monkeypatch.setenv("LQRO_QHULL_BIG", "1")
     N, H, box, seed = (32, 45, 3.0, 11) if case == "dense" else (64, 50, None, None)
     x, vg, out = _ref_step(lqro_mod, oracle, gains, N, H, box, seed, steps=2)
     T, NCF = oracle.tables(gains["A"], gains["B"], gains["L"], gains["E"], H)
@@ -111,9 +127,13 @@ def test_qhull_order_step_vs_oracle(lqro_mod, oracle, gains, case):
     oracle.set_hull_rule(1, round16=True)
     oracle.carry_normal(np.zeros(3))
     try:
-        for v, r, st, carry in out:
+        for v, r, st, carry, builds in out:
             rv, rr = oracle.step(T, NCF, S, x, vg, threads=8)
             assert st["hull_fail"] == 0
+            if big:   # (the switch was read: k_qhull_big built every hull)
+                assert len(builds) > 0 and (builds["kernel"] == 1).all()
+            if case == "dense":   # (the input covers the stale branch)
+                assert (r["flags"] & lqro_mod.REC_STALE).any()
             for f in ("n_reach", "flags", "facet", "n_facets", "dist", "normal", "plane_point", "plane_normal"):
                 a, b = r[f], rr[f]
                 if f == "flags":
@@ -133,7 +153,7 @@ def test_qhull_order_vs_reference_loop(lqro_mod, oracle, gains, case):
     N, H, box, seed = {"dense": (32, 45, 3.0, 11), "c2": (64, 50, None, None),
                        "c3": (1024, 100, None, None), "crowd22": (1024, 100, 22.0, 7)}[case]
     x, vg, out = _ref_step(lqro_mod, oracle, gains, N, H, box, seed)
-    v, r, st, _ = out[0]
+    v, r, st, _, _ = out[0]
     g = d[f"{case}_pairs"]
     ins = r[(r["flags"] & lqro_mod.REC_INSIDE) != 0]
     bad = ins[(ins["flags"] & lqro_mod.REC_HULLFAIL) != 0]
