@@ -253,6 +253,55 @@ int lqro_set_user_planes_device(lqro_ctx* ctx, const float* d_planes, int32_t ma
  * hi[a]: LQRO_E_ARG. */
 int lqro_set_fence(lqro_ctx* ctx, const double lo[3], const double hi[3], double tau);
 
+/* ---- obstacles: columns of the pair loop that are not agents -----------
+ * The reference's loop was written to run its pipeline once more, after the
+ * j loop, against a body that is no quadrotor (floorState / floorPoints,
+ * LQRO:1377-1379 and the commented block LQRO:1421-1434: createObstacle, GJK /
+ * convexHull, then createHalfPlanes WITHOUT the distance *= 0.5 of :1416,
+ * before the row's calculateNewV).  These calls generalise that block to M
+ * bodies: row agent i's pair loop visits the columns j = 0..n_agents-1, j != i
+ * as before, then j = n_agents + o for obstacle o = 0..M-1, in that order.
+ * An obstacle is one state of x_dim doubles ([0..2] position, [3..5]
+ * velocity, the rest as the caller's model has them: hover attitude and
+ * nominal rotor forces make x_i - x_o a position / velocity difference) and
+ * is treated exactly as the reference treats "the other agent":
+ * Translate_k = -C F_k (x_i - x_o) with the row agent's own tables, so a
+ * moving obstacle is extrapolated like an agent holding its velocity.
+ * Obstacles have no gains, no vgoal and never own a row.
+ *   - responsibility in (0, 1] replaces the 0.5 of LQRO:1416 for an obstacle
+ *     column (1.0: the agent does all the avoiding, LQRO:1434; 0.5: an
+ *     obstacle column is bit-identical to an agent column);
+ *   - the obstacle columns' point set is createSpheres (LQRO:735-750) with
+ *     2*XYRADIUS replaced by (xy_radius + obs_xy_radius) and 2*ZRADIUS by
+ *     (z_radius + obs_z_radius), the sum formed first: obstacle radii equal
+ *     to the agents' give the agents' set bit for bit, radii (0, 0) give
+ *     createFloorSpheres (LQRO:752-767), a point obstacle.  One shape and one
+ *     responsibility per context.
+ * A row then has n_agents - 1 + M slots: the loop-carried normalVector
+ * (LQRO:1385) runs through the obstacle columns like through any pair, the
+ * row's LP sees their planes after the agents' (fence and user planes stay
+ * ahead), and records (j = n_agents + o), statistics, hull builds, hull
+ * failures and merge suspects count them like pairs.  With lqro_set_neighbors
+ * the obstacles are candidates like agents (K = min(max_neighbors, n_agents
+ * + M - 1)).  Every row shard takes the same obstacles.  n_obstacles <= 0 or
+ * a null pointer clears and returns the context to the sizes and state of
+ * one that never had obstacles.  Radii negative or not finite, or a
+ * responsibility outside (0, 1]: LQRO_E_ARG.  LQRO_E_STATE while a
+ * lqro_step_device_begin is pending; waits for the last enqueued step before
+ * it replaces a buffer.  Changing M renumbers the pair slots: what the
+ * schedule kept per slot is reset, the carried normal stays.  With nothing
+ * set the step is the reference's; once set, results CHANGE against the
+ * reference. */
+int lqro_set_obstacles(lqro_ctx* ctx, const double* states /* M*X, host, copied */, int32_t n_obstacles,
+                       double obs_xy_radius, double obs_z_radius, double responsibility);
+/* The same with the states device-resident: d_states is read when the step
+ * runs, so the caller keeps it alive and writes it on the stream the step is
+ * enqueued on, before the step — the path for obstacles that move every
+ * step (lqro_set_user_planes_device's contract). */
+int lqro_set_obstacles_device(lqro_ctx* ctx, const double* d_states /* M*X, read when the step runs */,
+                              int32_t n_obstacles, double obs_xy_radius, double obs_z_radius,
+                              double responsibility);
+
 /* One control step: the pair loop LQRO:1393-1436 for the context's rows.
  * x: n_agents*X agent states (Quadrotor::x), vgoal: n_agents*3,
  * newv: n_agents*3 (only rows [row_begin,row_end) are written).  Host
@@ -311,7 +360,8 @@ int lqro_set_carry_normal(lqro_ctx* ctx, const double* n3);
 int lqro_get_carry_normal(lqro_ctx* ctx, double* n3);
 
 /* Per-pair records of the last step (LQRO_FLAG_RECORDS): rows
- * [row_begin,row_end) x (n_agents-1) neighbours in j order. */
+ * [row_begin,row_end) x (n_agents-1) neighbours in j order, then the row's
+ * obstacle columns (lqro_set_obstacles: j = n_agents + o). */
 int lqro_get_records(lqro_ctx* ctx, lqro_pair_record* out, int64_t capacity, int64_t* n_out);
 
 /* Counters of the last step: [0]=pairs, [1]=planes, [2]=inside, [3]=hull ok,

@@ -172,6 +172,18 @@ class ShardedSimulator {
     check(lqro_set_user_planes(ctx_, flat.data(), offs.data()), "lqro_set_user_planes");
   }
 
+  // Simulator::setObstacles for this rank's context: every rank passes the
+  // same obstacles (columns of every row's pair loop, lqro_set_obstacles)
+  void setObstacles(const std::vector<std::array<double, kX>>& states, double xy_radius, double z_radius,
+                    double responsibility = 1.0) {
+    if (!ctx_) return;
+    std::vector<double> flat;
+    for (const auto& st : states) flat.insert(flat.end(), st.begin(), st.end());
+    check(lqro_set_obstacles(ctx_, flat.empty() ? nullptr : flat.data(), (int32_t)states.size(), xy_radius, z_radius,
+                             responsibility),
+          "lqro_set_obstacles");
+  }
+
   // One iteration of LQRO:1393-1446 for this rank's rows, then the state
   // exchange; returns the next seed of the rand() stream.  Enqueued only:
   // download() waits for it.

@@ -143,6 +143,22 @@ class Simulator {
     check(lqro_set_user_planes(ctx_, flat.data(), offs.data()), "lqro_set_user_planes");
   }
 
+  // Obstacles: bodies that are not agents as extra columns of every agent's
+  // pair loop (lqro_set_obstacles; the reference's commented floor block,
+  // LQRO:1377-1379, 1421-1434).  One state of kX doubles each (position
+  // [0..2], velocity [3..5], hover trim otherwise); radii of the obstacles'
+  // ellipsoid ((0, 0): a point, LQRO:752-767); responsibility in (0, 1] for
+  // the 0.5 of LQRO:1416 (1.0: the agent does all the avoiding).  An empty
+  // vector clears.  Results change against the reference once set.
+  void setObstacles(const std::vector<std::array<double, kX>>& states, double xy_radius, double z_radius,
+                    double responsibility = 1.0) {
+    std::vector<double> flat;
+    for (const auto& st : states) flat.insert(flat.end(), st.begin(), st.end());
+    check(lqro_set_obstacles(ctx_, flat.empty() ? nullptr : flat.data(), (int32_t)states.size(), xy_radius, z_radius,
+                             responsibility),
+          "lqro_set_obstacles");
+  }
+
   // The pair loop LQRO:1393-1436 on the GPU: every Quadrotor::newV.
   // LQRO_E_HULL (a pair without its half-plane) and LQRO_E_QHMERGE (a pair
   // whose winning facet qconvex's pre-merge may join: its half-plane is not

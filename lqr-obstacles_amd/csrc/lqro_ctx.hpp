@@ -23,7 +23,7 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   lqro_config cfg;
   double *d_R, *d_TF, umax;
   unsigned long long* d_shash;
-  int rb, re, rs, nrows, npr;   // rows rb, rb + rs, ... < re
+  int rb, re, rs, nrows, npr;   // rows rb, rb + rs, ... < re; npr: slots a row (n_agents - 1 + nobs)
   int have_gains, per_agent;
   hipStream_t stream;
   hipEvent_t ev[5];
@@ -97,9 +97,24 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   float* d_uown;                  // lqro_set_user_planes's copies
   int* d_ucown;
   int lp_cap;
+  // obstacle columns (lqro_set_obstacles[_device]): nobs states behind the
+  // agents' in d_cols, the array the step's kernels then take for x (k_cols
+  // fills it at the head of every step)
+  int nobs;
+  const double* d_obs;            // nobs x X: the caller's, or d_obsown
+  double* d_obsown;               // lqro_set_obstacles's copy
+  double* d_cols;                 // (n_agents + nobs) x X
+  double obs_resp;                // the obstacle columns' factor for the 0.5 of LQRO:1416
+  int obs_shape;                  // 1: a point set of their own (d_So, d_Ro; pa.orad*, pa.oumax), 0: the agents'
+  double *d_So, *d_Ro;            // NP x 3; n_agents x H (the row of agent 0 with shared gains)
+  int lds_attr;                   // the dynamic LDS size the k_pair instantiations are set to
   lqro::PairArgs pa;
   lqro::DevPool mem;              // owns every d_* buffer above that is not the caller's
 };
+
+namespace lqro {
+void sphere_axes(int np, double axy, double az, double* out);   // (lqro_synth.cpp)
+}
 
 // the last step's final event was recorded on whichever stream it was
 // enqueued on (the caller's for lqro_step_device): wait on that, not on

@@ -367,7 +367,7 @@ __device__ __forceinline__ void hull_select(const HullArgs& A, const Mem& M, LT&
     if (retry) {
       // written by k_hull_big
     } else if (ok) {
-      const double dh = distance * 0.5;                  // :1416
+      const double dh = distance * hull_factor(A, slot);   // :1416
       const double mult = 1.0;                           // :1213
       pl[0] = (float)(xi[3] + mult * dh * nrm[0]);
       pl[1] = (float)(xi[4] + mult * dh * nrm[1]);

@@ -112,7 +112,41 @@ struct HullArgs {
   // own LDS (rows of at most LQRO_EARLY_LP_MAX_NPR pairs); 0: such rows are
   // left to the tail
   int row_lp;
+  // obstacle columns (lqro_set_obstacles; So null: none): x holds the agents'
+  // states, then the obstacles'; a row's slots jj >= obs_jj (= agents - 1) are
+  // the obstacles', with their own point set So (== S for the agents' shape)
+  // and obs_resp for the 0.5 of LQRO:1416
+  const double* So;
+  int obs_jj;
+  double obs_resp;
 };
+
+// Which of a row's slots are obstacle columns, for the kernels that finish a
+// half-plane outside the hull kernels (k_stale, k_stale_rows): slot jj >= jj
+// (through nbr_list with culling on) takes resp.  on null: no obstacles.
+struct ObsSlots {
+  const void* on;
+  const int* nbr_list;
+  int jj;
+  double resp;
+};
+
+// the factor of LQRO:1416 for a slot's half-plane: 0.5 between agents, the
+// context's responsibility for an obstacle column (LQRO:1434: 1.0)
+__device__ __forceinline__ double slot_factor(const int* nbr_list, int npr, long slot, const void* have_obs,
+                                              int obs_jj, double obs_resp) {
+  if (!have_obs) return 0.5;
+  const int jj = nbr_list ? nbr_list[slot] : (int)(slot % npr);
+  return jj >= obs_jj ? obs_resp : 0.5;
+}
+__device__ __forceinline__ double hull_factor(const HullArgs& A, int slot) {
+  return slot_factor(A.nbr_list, A.npr, slot, A.So, A.obs_jj, A.obs_resp);
+}
+// the point set of the column whose state is xj (x's rows past the agents'
+// are the obstacles')
+__device__ __forceinline__ const double* hull_col_sphere(const HullArgs& A, const double* xj) {
+  return (A.So && xj >= A.x + ((size_t)A.obs_jj + 1) * A.X) ? A.So : A.S;
+}
 
 // (LQRO_ROW_BIG, lqro_device.hpp: the row counter's protocol; the early LP
 // runs in k_qhull's facet-plane LDS: rows of at most LQRO_EARLY_LP_MAX_NPR
@@ -328,6 +362,7 @@ __device__ __forceinline__ int hull_points(const HullArgs& A, LT& L, const doubl
                                            const double* xi, const double* xj, const double* vrel,
                                            double* Pr, double* Pf) {
   const int tid = threadIdx.x;
+  const double* Sj = hull_col_sphere(A, xj);
   if (tid == 0) { L.n = A.ext_pts ? A.ext_n : 0; L.fail = 0; }
   hl_bar();
   if (A.ext_pts)
@@ -354,7 +389,7 @@ __device__ __forceinline__ int hull_points(const HullArgs& A, LT& L, const doubl
         const int k = q / A.NP, p = q % A.NP;
         const double* Tk = Ti + (size_t)k * 9;
         const double* tk = L.tr + (k - k0) * 3;
-        const double u0 = A.S[3 * p] + tk[0], u1 = A.S[3 * p + 1] + tk[1], u2 = A.S[3 * p + 2] + tk[2];
+        const double u0 = Sj[3 * p] + tk[0], u1 = Sj[3 * p + 1] + tk[1], u2 = Sj[3 * p + 2] + tk[2];
         p0 = ((0.0 + Tk[0] * u0) + Tk[1] * u1) + Tk[2] * u2;
         p1 = ((0.0 + Tk[3] * u0) + Tk[4] * u1) + Tk[5] * u2;
         p2 = ((0.0 + Tk[6] * u0) + Tk[7] * u1) + Tk[8] * u2;

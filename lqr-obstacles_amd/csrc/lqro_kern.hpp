@@ -57,10 +57,16 @@ struct FenceArgs {
 
 namespace lqro {
 struct HullArgs;
+struct ObsSlots;   // (lqro_hull_job.hpp)
 // k_tables: one workgroup per agent with gains of its own (n_gains: 1 or N)
 void launch_tables(hipStream_t s, int n_gains, int X, int U, int H, const double* A, const double* B, const double* L,
                    const double* E, int per_agent, double* T, double* NCF, double* R, double* TF, double rad0,
                    double rad1, double rad2, double umax, int* err);
+// k_obs_rtab: the obstacle columns' slice bound (PairArgs::Ro) from the tables' T
+void launch_obs_rtab(hipStream_t s, int n_gains, int H, const double* T, double* Ro, double rad0, double rad1,
+                     double rad2, double umax);
+// k_cols: the step's columns, the agents' states then the obstacles'
+void launch_cols(hipStream_t s, const double* x, size_t nx, const double* obs, size_t nobs, double* cols);
 constexpr size_t kLpLdsMax = 160 * 1024;   // one CU's LDS: the longest plane list k_lp_lds holds
 // the LP of every row: k_lp_lds (+ k_lp4 for the rows it lists) or, past
 // kLpLdsMax, k_lp.  La.lp4_count / lp4_next must be zero (or lp4_list null).
@@ -91,12 +97,12 @@ size_t qhull_worker_bytes(int hnp);
 // k_stale: the facet-0 pairs' loop-carried normals, then the carry out
 void launch_stale(hipStream_t s, float* planes, const double* qnrm, const int* list, const int* count, int cap,
                   const double* x, int X, int npr, int row_begin, int row_stride, double* carry,
-                  lqro_pair_record* recs, long nslots);
+                  lqro_pair_record* recs, long nslots, const ObsSlots& O);
 void launch_rowlast(hipStream_t s, const float* planes, const double* qnrm, int npr, int nrows, int row_begin,
                     int row_stride, double* rowtab);
 void launch_stale_rows(hipStream_t s, float* planes, const double* qnrm, const int* list, const int* count, int cap,
                        const double* x, int X, int npr, int row_begin, int row_stride, const double* rowtab, int N,
-                       double* carry, lqro_pair_record* recs, long nslots);
+                       double* carry, lqro_pair_record* recs, long nslots, const ObsSlots& O);
 // controlMatrices for n models into out (stride X*X + 12X + 25 doubles):
 // k_synthw (one wave per agent) or, lane = true, k_synth (one agent per lane)
 void launch_synth(int x_dim, bool lane, const lqro_model* d_models, int n, double* d_out);

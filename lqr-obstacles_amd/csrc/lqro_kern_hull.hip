@@ -71,9 +71,9 @@ size_t qhull_worker_bytes(int hnp) {
 
 void launch_stale(hipStream_t s, float* planes, const double* qnrm, const int* list, const int* count, int cap,
                   const double* x, int X, int npr, int row_begin, int row_stride, double* carry,
-                  lqro_pair_record* recs, long nslots) {
+                  lqro_pair_record* recs, long nslots, const ObsSlots& O) {
   hipLaunchKernelGGL(k_stale, dim3(16), dim3(64), 0, s, planes, qnrm, list, count, cap, x, X, npr, row_begin,
-                     row_stride, carry, recs, nslots);
+                     row_stride, carry, recs, nslots, O);
 }
 
 void launch_rowlast(hipStream_t s, const float* planes, const double* qnrm, int npr, int nrows, int row_begin,
@@ -84,10 +84,10 @@ void launch_rowlast(hipStream_t s, const float* planes, const double* qnrm, int 
 
 void launch_stale_rows(hipStream_t s, float* planes, const double* qnrm, const int* list, const int* count, int cap,
                        const double* x, int X, int npr, int row_begin, int row_stride, const double* rowtab, int N,
-                       double* carry, lqro_pair_record* recs, long nslots) {
+                       double* carry, lqro_pair_record* recs, long nslots, const ObsSlots& O) {
   (void)nslots;
   hipLaunchKernelGGL(k_stale_rows, dim3(16), dim3(64), 0, s, planes, qnrm, list, count, cap, x, X, npr, row_begin,
-                     row_stride, rowtab, N, carry, recs);
+                     row_stride, rowtab, N, carry, recs, O);
 }
 
 }  // namespace lqro

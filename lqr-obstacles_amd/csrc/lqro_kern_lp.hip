@@ -266,7 +266,44 @@ __global__ void __launch_bounds__(256) k_fence(FenceArgs F) {
     }
   }
 }
+// The obstacle columns' slice bound (lqro_set_obstacles with a shape of its
+// own): k_tables' R with the obstacles' semi-axes, from the T it left.
+__global__ void __launch_bounds__(256) k_obs_rtab(int n, const double* __restrict__ T, double* __restrict__ Ro,
+                                                  double rad0, double rad1, double rad2, double umax) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;   // (agent, k)
+  if (q >= n) return;
+  const double* inv = T + (size_t)q * 9;
+  const double rad[3] = {rad0, rad1, rad2};
+  double fr = 0.0;
+  for (int rr = 0; rr < 3; ++rr)
+    for (int cc = 0; cc < 3; ++cc) {
+      const double tv = inv[rr * 3 + cc];
+      fr += (tv * rad[cc]) * (tv * rad[cc]);
+    }
+  Ro[q] = sqrt(fr) * umax * (1.0 + 1e-12);
+}
+
+// The step's columns in one array: the agents' states, then the obstacles'
+// (the kernels address column j at x + j X).
+__global__ void __launch_bounds__(256) k_cols(const double* __restrict__ x, size_t nx,
+                                              const double* __restrict__ obs, size_t nobs,
+                                              double* __restrict__ cols) {
+  const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < nx) cols[q] = x[q];
+  else if (q < nx + nobs) cols[q] = obs[q - nx];
+}
+
 namespace lqro {
+
+void launch_obs_rtab(hipStream_t s, int n_gains, int H, const double* T, double* Ro, double rad0, double rad1,
+                     double rad2, double umax) {
+  const int n = n_gains * H;
+  hipLaunchKernelGGL(k_obs_rtab, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, T, Ro, rad0, rad1, rad2, umax);
+}
+
+void launch_cols(hipStream_t s, const double* x, size_t nx, const double* obs, size_t nobs, double* cols) {
+  hipLaunchKernelGGL(k_cols, dim3((unsigned)((nx + nobs + 255) / 256)), dim3(256), 0, s, x, nx, obs, nobs, cols);
+}
 
 void launch_tables(hipStream_t s, int n_gains, int X, int U, int H, const double* A, const double* B, const double* L,
                    const double* E, int per_agent, double* T, double* NCF, double* R, double* TF, double rad0,

@@ -443,7 +443,8 @@ __device__ __forceinline__ int lh_points(const HullArgs& A, LHullL& L, const dou
   double* str = sT + H * 9;
   double* sS = str + H * 3;
   for (int q = tid; q < H * 9; q += bd) sT[q] = Ti[q];
-  for (int q = tid; q < NP * 3; q += bd) sS[q] = A.S[q];
+  const double* Sj = hull_col_sphere(A, xj);
+  for (int q = tid; q < NP * 3; q += bd) sS[q] = Sj[q];
   for (int it = tid; it < 3 * H; it += bd) {
     const int k = it / 3, r = it % 3;
     double d = 0.0;

@@ -14,7 +14,7 @@ using namespace lqro;
 
 extern "C" {
 
-int lqro_version(void) { return 2; }
+int lqro_version(void) { return 3; }
 
 const char* lqro_status_string(int s) {
   switch (s) {

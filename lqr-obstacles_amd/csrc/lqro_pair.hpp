@@ -82,8 +82,20 @@ struct PairArgs {
   const int* nbr_list;                // culling on: per row npr (= K) neighbour jj, ascending, -1 = none
   double* qnrm;                       // LQRO_FLAG_QHULL_ORDER: per slot normal, dist (k_stale reads them)
   int* rowpend;                       // early LP: per row open work (LQRO_ROW_BIG), null: off
+  // obstacle columns (lqro_set_obstacles): x then holds the agents' states
+  // followed by the obstacles', and a row's slots jj >= obs_jj (= agents - 1)
+  // are the obstacles' (INT_MAX: none).  They take obs_resp for the 0.5 of
+  // LQRO:1416 and their own point set: So (NP x 3), its semi-axes and max |u_p|,
+  // Ro (per agent H, as R).  A shape equal to the agents' shares S, R and
+  // their LDS (lds_So == lds_S, lds_Ro == lds_R)
+  int obs_jj;
+  double obs_resp;
+  double orad0, orad1, orad2, oumax;
+  const double* So;
+  const double* Ro;
   // LDS layout, in doubles
   int XP, lds_T, lds_N, lds_S, lds_R, lds_TF, lds_H, lds_wave, wave_doubles;
+  int lds_So, lds_Ro;                 // behind lds_H when the obstacles have a shape of their own
 };
 
 struct BlockTabs {
@@ -232,6 +244,7 @@ struct SliceSupport {
 #ifdef LQRO_PAIR_PROFILE
   unsigned long long* pc;   // [0] support cycles, [1] calls, [2] candidate slices, [3] Johnson, [4] witness, [5] point
 #endif
+  double rad0, rad1, rad2, umax;   // the column's sphere: semi-axes and max |u_p| (the agents' or the obstacles')
 
   __device__ void point(int q, double* x) const {
     const int k = q / P.NP;
@@ -349,12 +362,12 @@ struct SliceSupport {
         const double w0 = Tk[0] * d0 + Tk[3] * d1 + Tk[6] * d2;
         const double w1 = Tk[1] * d0 + Tk[4] * d1 + Tk[7] * d2;
         const double w2 = Tk[2] * d0 + Tk[5] * d1 + Tk[8] * d2;
-        const double a0 = P.rad0 * w0, a1 = P.rad1 * w1, a2 = P.rad2 * w2;
+        const double a0 = rad0 * w0, a1 = rad1 * w1, a2 = rad2 * w2;
         // c_k.d = (T_k tr_k).d = tr_k.(T_k^T d); the reassociation error is
         // ~1e-16 |tr| ||T|| |d|, far inside the 1e-9 dn sc margin
         const double* tk = W.tr + 3 * k;
         ub = tk[0] * w0 + tk[1] * w1 + tk[2] * w2 +
-             __builtin_amdgcn_sqrt(a0 * a0 + a1 * a1 + a2 * a2) * P.umax + 1e-9 * dn * W.sc[k];
+             __builtin_amdgcn_sqrt(a0 * a0 + a1 * a1 + a2 * a2) * umax + 1e-9 * dn * W.sc[k];
         if (ub > cu) { cu = ub; ck = k; }
       }
       ubr[s] = ub;
@@ -478,6 +491,8 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
   double* sS = lds + P.lds_S;
   double* sR = lds + P.lds_R;
   double* sTF = lds + P.lds_TF;
+  double* sSo = lds + P.lds_So;   // (== sS, sR unless the obstacles have a shape of their own)
+  double* sRo = lds + P.lds_Ro;
   unsigned long long* sH = reinterpret_cast<unsigned long long*>(lds + P.lds_H);
   BlockTabs B;
   B.T = sT; B.N = sN; B.S = sS; B.R = sR; B.TF = sTF; B.shash = sH; B.pitch = XP;
@@ -502,9 +517,6 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
   if (has_region && lane < 5) W.st[lane] = 0;
 #ifdef LQRO_PAIR_PROFILE
   unsigned long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  SliceSupport sup{P, B, W, lane, pc};
-#else
-  SliceSupport sup{P, B, W, lane};
 #endif
 
   // one ordered pair (i, j = jj-th other agent) of local row lrow
@@ -512,11 +524,6 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
     // the lane id, opaque per pair: lane-derived constants are rebuilt here
     // rather than hoisted into registers held across the persistent loop
     const int ln = opaque(lane);
-#ifdef LQRO_PAIR_PROFILE
-    SliceSupport sp{P, B, W, ln, pc};
-#else
-    SliceSupport sp{P, B, W, ln};
-#endif
     const double* xi = P.x + (size_t)i * X;
     // culling on (lqro_set_neighbors): slot q of the row holds its q-th neighbour
     const int jq = P.nbr_list != nullptr ? P.nbr_list[(size_t)lrow * P.npr + jj] : jj;
@@ -536,6 +543,22 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
       return;
     }
     const int j = jq < i ? jq : jq + 1;
+    // an obstacle column: its own sphere and slice bound (in the same LDS
+    // tables when the shape is the agents')
+    const bool obs = jq >= P.obs_jj;
+    BlockTabs Bj = B;
+    if (obs) {
+      Bj.S = sSo;
+      if constexpr (HOT == kHotPerAgent) Bj.R = P.Ro + (size_t)i * H;
+      else Bj.R = sRo;
+    }
+#ifdef LQRO_PAIR_PROFILE
+    SliceSupport sp{P, Bj, W, ln, pc, obs ? P.orad0 : P.rad0, obs ? P.orad1 : P.rad1, obs ? P.orad2 : P.rad2,
+                    obs ? P.oumax : P.umax};
+#else
+    SliceSupport sp{P, Bj, W, ln, obs ? P.orad0 : P.rad0, obs ? P.orad1 : P.rad1, obs ? P.orad2 : P.rad2,
+                    obs ? P.oumax : P.umax};
+#endif
     const double* xj = P.x + (size_t)j * X;
     double d[X];
 #pragma unroll
@@ -548,8 +571,8 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
 
     // 1. per slice: Translate (exact), centre, class       (lanes <-> k)
     for (int k = ln; k < H; k += 64) {
-      const int np = HOT == kHotPerAgent ? B.pitch : XP;
-      const double* nc = B.N + (size_t)k * 3 * np;
+      const int np = HOT == kHotPerAgent ? Bj.pitch : XP;
+      const double* nc = Bj.N + (size_t)k * 3 * np;
       double t0 = 0.0, t1 = 0.0, t2 = 0.0;
 #pragma unroll
       for (int c = 0; c < X; ++c) t0 += nc[c] * d[c];
@@ -558,15 +581,15 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
 #pragma unroll
       for (int c = 0; c < X; ++c) t2 += nc[2 * np + c] * d[c];
       W.tr[3 * k] = t0; W.tr[3 * k + 1] = t1; W.tr[3 * k + 2] = t2;
-      const double* Tk = B.T + 9 * k;
+      const double* Tk = Bj.T + 9 * k;
       const double c0 = Tk[0] * t0 + Tk[1] * t1 + Tk[2] * t2;
       const double c1 = Tk[3] * t0 + Tk[4] * t1 + Tk[5] * t2;
       const double c2 = Tk[6] * t0 + Tk[7] * t1 + Tk[8] * t2;
-      const double Rk = B.R[k];
+      const double Rk = Bj.R[k];
       // magnitudes for the 1e-9 relative margins: the hardware square root
       // (error a few ulp) suffices; |vrel| covers dc's own rounding
       const double sc = __builtin_amdgcn_sqrt(c0 * c0 + c1 * c1 + c2 * c2) + Rk +
-                        B.TF[k] * __builtin_amdgcn_sqrt(t0 * t0 + t1 * t1 + t2 * t2) + 1.0;
+                        Bj.TF[k] * __builtin_amdgcn_sqrt(t0 * t0 + t1 * t1 + t2 * t2) + 1.0;
       W.sc[k] = sc;
       const double e0 = c0 - vrel[0], e1 = c1 - vrel[1], e2 = c2 - vrel[2];
       const double dc = __builtin_amdgcn_sqrt(e0 * e0 + e1 * e1 + e2 * e2);
@@ -583,7 +606,7 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
           W.mask[k * P.PW + pw] = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
         }
       if (RECS) W.cnt[k] = cls == kSliceIn ? NP : 0;
-      if (cls == kSliceIn) hsh += B.shash[k];
+      if (cls == kSliceIn) hsh += Bj.shash[k];
     }
     wave_lds_sync();
     PSTAMP(1);
@@ -613,7 +636,7 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
       while (mm) {
         const int k = 64 * s + __ffsll((long long)mm) - 1;
         mm &= mm - 1ull;
-        const double* Tk = B.T + 9 * k;
+        const double* Tk = Bj.T + 9 * k;
         const double* tk = W.tr + 3 * k;
         double T[9];
 #pragma unroll
@@ -626,9 +649,9 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
           ok[pw] = false;
           if (pw < P.PW && p < NP) {
             // exact_point (LQRO:776, matrix.h:223-227)
-            const double u0 = B.S[p] + t0;
-            const double u1 = B.S[NP + p] + t1;
-            const double u2 = B.S[2 * NP + p] + t2;
+            const double u0 = Bj.S[p] + t0;
+            const double u1 = Bj.S[NP + p] + t1;
+            const double u2 = Bj.S[2 * NP + p] + t2;
             const double x0 = ((0.0 + T[0] * u0) + T[1] * u1) + T[2] * u2;
             const double x1 = ((0.0 + T[3] * u0) + T[4] * u1) + T[5] * u2;
             const double x2 = ((0.0 + T[6] * u0) + T[7] * u1) + T[8] * u2;
@@ -684,7 +707,7 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
       flags = LQRO_REC_PLANE | (inside ? LQRO_REC_INSIDE : 0) | (go.backup ? LQRO_REC_BACKUP : 0);
       dist = distance;
       if (!inside) {
-        distance *= 0.5;                                        // :1416
+        distance *= obs ? P.obs_resp : 0.5;                     // :1416 (an obstacle: LQRO:1434)
         const double mult = -1.0;                               // :1215
         pl[0] = (float)(xi[3] + mult * distance * nrm[0]);      // :1217
         pl[1] = (float)(xi[4] + mult * distance * nrm[1]);
@@ -777,8 +800,12 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
         sR[q] = P.R[q];
         sTF[q] = P.TF[q];
       }
+      if (P.lds_Ro != P.lds_R)
+        for (int q = threadIdx.x; q < H; q += blockDim.x) sRo[q] = P.Ro[q];
     }
     for (int q = threadIdx.x; q < NP * 3; q += blockDim.x) sS[(q % 3) * NP + q / 3] = P.S[q];
+    if (P.lds_So != P.lds_S)
+      for (int q = threadIdx.x; q < NP * 3; q += blockDim.x) sSo[(q % 3) * NP + q / 3] = P.So[q];
     for (int q = threadIdx.x; q < H; q += blockDim.x) sH[q] = P.shash[q];
     __syncthreads();
     const int nhot = min(*P.hot_count, P.hot_cap);
@@ -847,6 +874,11 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
         sR[q] = Ri[q];
         sTF[q] = TFi[q];
         sH[q] = P.shash[q];
+      }
+      if (P.lds_So != P.lds_S) {   // the obstacle columns' sphere and slice bound
+        const double* Roi = P.Ro + ag * H;
+        for (int q = threadIdx.x; q < NP * 3; q += blockDim.x) sSo[(q % 3) * NP + q / 3] = P.So[q];
+        for (int q = threadIdx.x; q < H; q += blockDim.x) sRo[q] = Roi[q];
       }
       staged = ag;
       __syncthreads();

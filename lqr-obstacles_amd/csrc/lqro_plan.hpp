@@ -126,6 +126,8 @@ struct StepShape {
   int early_lp_max_npr;      // LQRO_EARLY_LP_MAX_NPR
   int row_big;               // LQRO_ROW_BIG
   int extra_planes = 0;      // fence + user planes a row's LP may get ahead of its pair planes (capacity per row)
+  int n_obs = 0;             // obstacle columns behind the npr agent columns of every row (lqro_set_obstacles):
+                             //   a row has npr + n_obs slots, whatever the number of rows
 };
 
 struct StepPlan {
@@ -171,7 +173,9 @@ inline int qhull_side_balance(int n, double w_sweep, double w_build, double b_ma
 inline StepPlan plan_step(const StepShape& S, const StepKnobs& K, const StepFeedback& F, bool known) {
   StepPlan p{};
   // culling on: each row's slots are its K neighbours (k_nbr), not its N-1 pairs
-  const int npr = S.nbr_k > 0 ? std::min(S.nbr_k, S.npr) : S.npr;
+  // (columns that are not rows: the obstacles' slots count like pair slots everywhere below)
+  const int cols = S.npr + S.n_obs;
+  const int npr = S.nbr_k > 0 ? std::min(S.nbr_k, cols) : cols;
   p.npr = npr;
   // the LDS hull variant packs outside-set extents in 32 bits (lqro_hull.hpp
   // seg_put: 15-bit count, 17-bit offset / 4 into HULL_SBMULT * H*NP entries)

@@ -1236,7 +1236,7 @@ __device__ __forceinline__ bool qsel_commit(const HullArgs& A, int slot, const d
   double nrm[3] = {0.0, 0.0, 0.0};
   if (ok && !stale) {
     nrm[0] = bn[0]; nrm[1] = bn[1]; nrm[2] = bn[2];
-    const double dh = best * 0.5;                      // :1416
+    const double dh = best * hull_factor(A, slot);     // :1416
     const double mult = 1.0;                           // :1213
     pl[0] = (float)(xi[3] + mult * dh * nrm[0]);
     pl[1] = (float)(xi[4] + mult * dh * nrm[1]);
@@ -1441,7 +1441,8 @@ __device__ __forceinline__ bool qh_slot_normal(const float* planes, const double
 #ifdef LQRO_HULL_TU   // the kernels: defined once, in lqro_kern_hull.hip
 __global__ void __launch_bounds__(64) k_stale(float* planes, const double* qnrm, const int* list, const int* count,
                                               int cap, const double* x, int X, int npr, int row_begin,
-                                              int row_stride, double* carry, lqro_pair_record* recs, long nslots) {
+                                              int row_stride, double* carry, lqro_pair_record* recs, long nslots,
+                                              ObsSlots O) {
   const int lane = threadIdx.x & 63;
   const int n = min(*count, cap);
   for (int e = blockIdx.x; e <= n; e += gridDim.x) {
@@ -1465,7 +1466,7 @@ __global__ void __launch_bounds__(64) k_stale(float* planes, const double* qnrm,
     const int lrow = (int)(slot / npr);
     const int i = row_begin + lrow * row_stride;
     const double* xi = x + (size_t)i * X;
-    const double dh = qnrm[(size_t)slot * 4 + 3] * 0.5;   // :1416
+    const double dh = qnrm[(size_t)slot * 4 + 3] * slot_factor(O.nbr_list, npr, slot, O.on, O.jj, O.resp);   // :1416
     const double mult = 1.0;                              // :1213
     float* pl = planes + (size_t)slot * 8;
     pl[0] = (float)(xi[3] + mult * dh * nrm[0]);
@@ -1529,7 +1530,7 @@ __device__ __forceinline__ int qh_row_before(const double* rowtab, int i) {
 __global__ void __launch_bounds__(64) k_stale_rows(float* planes, const double* qnrm, const int* list,
                                                    const int* count, int cap, const double* x, int X, int npr,
                                                    int row_begin, int row_stride, const double* rowtab, int N,
-                                                   double* carry, lqro_pair_record* recs) {
+                                                   double* carry, lqro_pair_record* recs, ObsSlots O) {
   const int lane = threadIdx.x & 63;
   const int n = min(*count, cap);
   for (int e = blockIdx.x; e <= n; e += gridDim.x) {
@@ -1560,7 +1561,7 @@ __global__ void __launch_bounds__(64) k_stale_rows(float* planes, const double* 
     }
     if (lane != 0) continue;
     const double* xi = x + (size_t)i * X;
-    const double dh = qnrm[(size_t)s0 * 4 + 3] * 0.5;   // :1416
+    const double dh = qnrm[(size_t)s0 * 4 + 3] * slot_factor(O.nbr_list, npr, s0, O.on, O.jj, O.resp);   // :1416
     const double mult = 1.0;                            // :1213
     float* pl = planes + (size_t)s0 * 8;
     pl[0] = (float)(xi[3] + mult * dh * nrm[0]);

@@ -64,10 +64,81 @@ void lqro_destroy(lqro_ctx* c) {
   delete c;
 }
 
+// The buffers pitched in pair slots (rows x slots a row), and the capacities
+// that follow them.  lqro_create allocates them; lqro_set_obstacles again when
+// the number of columns changes: the new set first (a failed call leaves the
+// context as it was), then the old one is released.
+struct SlotBufs {
+  float *d_planes, *d_lpscratch, *d_lpcompact;
+  lqro_pair_record* d_recs;
+  int *d_hq, *d_rq, *d_lq, *d_hotlist, *d_prevq, *d_qstale, *d_nbrlist;
+  unsigned char* d_hotmark;
+  double* d_qnrm;
+  int hull_cap, hot_cap, lp_cap, nbr_cap;
+};
+#define SLOT_BUFS(F) \
+  F(d_planes) F(d_lpscratch) F(d_lpcompact) F(d_recs) F(d_hq) F(d_rq) F(d_lq) F(d_hotlist) F(d_prevq) F(d_qstale) \
+  F(d_hotmark) F(d_qnrm)
+
+static void slots_release(lqro_ctx* c, SlotBufs& b) {
+#define F(m) c->mem.release(b.m);
+  SLOT_BUFS(F)
+#undef F
+  c->mem.release(b.d_nbrlist);
+}
+
+static int slots_alloc(lqro_ctx* c, int npr, SlotBufs& b) {
+  const lqro_config& g = c->cfg;
+  const size_t rows = (size_t)c->nrows, slots = rows * (size_t)npr;   // (both at least 1)
+  b = SlotBufs{};
+  b.lp_cap = npr + c->nfence + c->uplane_max;
+  // one entry per slot: a pair enqueues at most one hull job per step, so the
+  // queue cannot overflow (C5's 2048 x 16383-slot shard: 134 MB, of 288 GB)
+  b.hull_cap = (int)slots;
+  b.hot_cap = (int)std::max<size_t>(16384, slots / 32);
+  bool bad = false;
+#define SB(member, ...) bad = bad || c->mem.get(b.member, __VA_ARGS__) != 0
+  SB(d_planes, 8 * slots);
+  SB(d_lpscratch, 8 * rows * (size_t)b.lp_cap);
+  SB(d_lpcompact, 8 * rows * (size_t)b.lp_cap);
+  if (g.flags & LQRO_FLAG_RECORDS) SB(d_recs, slots);
+  SB(d_hq, slots);
+  SB(d_rq, slots);
+  SB(d_lq, slots);
+  SB(d_hotlist, (size_t)b.hot_cap);
+  // (k_prio keeps a mark of 2 it finds — k_prio_prev's "listed" — so the marks
+  // start at 0: the first split step after the plain ones would otherwise
+  // take recycled device memory's bytes for marks and skip those pairs)
+  SB(d_hotmark, slots, 0);
+  if (c->qhull_order) {
+    SB(d_qnrm, 4 * slots);
+    SB(d_qstale, slots, 0xFF);
+    SB(d_prevq, (size_t)b.hot_cap, 0xFF);
+  }
+  if (c->nbr_k > 0) {   // (culling on: the lists at the new K)
+    b.nbr_cap = std::min(c->nbr_k, npr);
+    SB(d_nbrlist, rows * (size_t)b.nbr_cap + 1);
+  }
+#undef SB
+  if (bad) { slots_release(c, b); return LQRO_E_NOMEM; }
+  return LQRO_OK;
+}
+
+// the context takes b (and npr) for its own; its old set goes
+static void slots_adopt(lqro_ctx* c, int npr, SlotBufs& b) {
+  SlotBufs old{};
+#define F(m) old.m = c->m; c->m = b.m;
+  SLOT_BUFS(F)
+#undef F
+  if (b.d_nbrlist) { old.d_nbrlist = c->d_nbrlist; c->d_nbrlist = b.d_nbrlist; c->nbr_cap = b.nbr_cap; }
+  slots_release(c, old);
+  c->npr = npr; c->hull_cap = b.hull_cap; c->hot_cap = b.hot_cap; c->lp_cap = b.lp_cap;
+}
+
 static int ctx_alloc(lqro_ctx* c) {
   const lqro_config& g = c->cfg;
   const size_t N = g.n_agents, X = g.x_dim, U = g.u_dim, H = g.horizon, NP = g.n_points;
-  const size_t rows = (size_t)c->nrows, slots = rows * c->npr;   // (both at least 1)
+  const size_t rows = (size_t)c->nrows;
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   for (int k = 0; k < 5; ++k) HIPCHK(hipEventCreate(&c->ev[k]));
   HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
@@ -87,17 +158,12 @@ static int ctx_alloc(lqro_ctx* c) {
   BUF(d_R, N * H);
   BUF(d_TF, N * H);
   BUF(d_shash, H);
-  BUF(d_planes, 8 * slots);
-  BUF(d_lpscratch, 8 * slots);
-  BUF(d_lpcompact, 8 * slots);
-  if (g.flags & LQRO_FLAG_RECORDS) BUF(d_recs, slots);
-  // one entry per slot: a pair enqueues at most one hull job per step, so the
-  // queue cannot overflow (C5's 2048 x 16383-slot shard: 134 MB, of 288 GB)
-  c->hull_cap = (int)slots;
-  BUF(d_hq, slots);
+  {
+    SlotBufs b;
+    if (int rc = slots_alloc(c, c->npr, b)) return rc;
+    slots_adopt(c, c->npr, b);
+  }
   BUF(d_hcount, LQRO_HC_WORDS);
-  BUF(d_rq, slots);
-  BUF(d_lq, slots);
   BUF(d_err, 1);
   BUF(d_stats, LQRO_ST_WORDS);
   HIPCHK(hipHostMalloc((void**)&c->h_feedback, 2 * sizeof(StepFeedback), hipHostMallocDefault));
@@ -117,12 +183,6 @@ static int ctx_alloc(lqro_ctx* c) {
   BUF(d_hbig, (size_t)c->hull_big_blocks);
   BUF(d_hwide, HULL_CWAVES * hb);
   BUF(d_hbag, HULL_BAGCAP * hb, 0xFF);
-  c->hot_cap = (int)std::max<size_t>(16384, slots / 32);
-  BUF(d_hotlist, (size_t)c->hot_cap);
-  // (k_prio keeps a mark of 2 it finds — k_prio_prev's "listed" — so the marks
-  // start at 0: the first split step after the plain ones would otherwise
-  // take recycled device memory's bytes for marks and skip those pairs)
-  BUF(d_hotmark, slots, 0);
   BUF(d_lp4, 6 * rows, 0);
   BUF(d_carry, 6, 0);
   BUF(d_rowpend, 2 * rows, 0);
@@ -133,14 +193,63 @@ static int ctx_alloc(lqro_ctx* c) {
     c->qworkers = c->n_cu;
     c->qstride = (qhull_worker_bytes((int)(H * NP)) + 255) & ~(size_t)255;
     BUF(d_qscratch, c->qstride * (size_t)c->qworkers, 0);   // k_qhull_big's visit stamps
-    BUF(d_qnrm, 4 * slots);
-    BUF(d_qstale, slots, 0xFF);
     BUF(d_hbuild, 4 * (size_t)LQRO_HBUILD_CAP, 0);
-    BUF(d_prevq, (size_t)c->hot_cap, 0xFF);
     BUF(d_hot2, LQRO_H2_WORDS, 0);
   }
 #undef BUF
   return LQRO_OK;
+}
+
+// LDS layout of k_pair (in doubles): block tables, then one region per wave.
+// obs_shape: the obstacle columns' own sphere and slice bound behind the
+// agents' tables (lqro_set_obstacles); without, the layout a context is
+// created with.  False when no wave's region fits.
+static bool pair_layout(const lqro_config& g, bool obs_shape, PairArgs& P, int& lds_bytes) {
+  const int H = g.horizon, NP = g.n_points, X = g.x_dim, XP = X + 1;
+  int off = 0;
+  P.XP = XP;
+  P.PW = (NP + 63) / 64;
+  P.lds_T = off; off += H * 9;
+  P.lds_N = off; off += H * 3 * XP;
+  P.lds_S = off; off += 3 * NP;
+  P.lds_R = off; off += H;
+  P.lds_TF = off; off += H;
+  P.lds_H = off; off += H;
+  P.lds_So = P.lds_S; P.lds_Ro = P.lds_R;
+  if (obs_shape) {
+    P.lds_So = off; off += 3 * NP;
+    P.lds_Ro = off; off += H;
+  }
+  P.lds_wave = off;
+  // tr 3H, sc H, mask H*PW (u64), cls/cnt/mixed 3H ints (mixed padded to
+  // even), GJK simplex 18, statistics 5
+  P.wave_doubles = 4 * H + H * P.PW + H + (H + (H & 1)) / 2 + 18 + 5;
+  const int budget = 160 * 1024 / 8;
+  int waves = (budget - off) / P.wave_doubles;
+  if (waves > LQRO_PAIR_LB / 64) waves = LQRO_PAIR_LB / 64;
+  if (waves < 1) return false;
+  P.waves = waves;
+  P.max_waves = waves;
+  off += waves * P.wave_doubles;
+  lds_bytes = off * 8;
+  return true;
+}
+
+static bool pair_set_lds(int lds_bytes) {
+  return pair_set_lds_t<16, false>(lds_bytes) && pair_set_lds_t<16, true>(lds_bytes) &&
+         pair_set_lds_t<12, false>(lds_bytes) && pair_set_lds_t<12, true>(lds_bytes);
+}
+
+// max |u_p| with s_p = diag(rad) u_p (createSpheres, :743-745), with the
+// bound's margin
+static double sphere_umax(const double* S, int NP, const double* rad) {
+  double um = 0.0;
+  for (int p = 0; p < NP; ++p) {
+    double u2 = 0.0;
+    for (int d = 0; d < 3; ++d) { const double u = S[3 * p + d] / rad[d]; u2 += u * u; }
+    um = std::max(um, std::sqrt(u2));
+  }
+  return um * (1.0 + 1e-12);
 }
 
 int lqro_create(const lqro_config* cfg, lqro_ctx** out) {
@@ -171,49 +280,23 @@ int lqro_create(const lqro_config* cfg, lqro_ctx** out) {
   if (c->rb < 0 || c->re > g.n_agents || c->rb >= c->re || g.row_stride < 0) { delete c; return LQRO_E_ARG; }
   c->nrows = (c->re - c->rb + c->rs - 1) / c->rs;
   c->npr = g.n_agents - 1;
-  c->lp_cap = c->npr;
-  // LDS layout of k_pair (in doubles): block tables, then one region per wave
-  const int H = g.horizon, NP = g.n_points, X = g.x_dim, XP = X + 1;
-  int off = 0;
+  const int H = g.horizon, NP = g.n_points;
   PairArgs& P = c->pa;
-  P.XP = XP;
-  P.PW = (NP + 63) / 64;
-  P.lds_T = off; off += H * 9;
-  P.lds_N = off; off += H * 3 * XP;
-  P.lds_S = off; off += 3 * NP;
-  P.lds_R = off; off += H;
-  P.lds_TF = off; off += H;
-  P.lds_H = off; off += H;
-  P.lds_wave = off;
-  // tr 3H, sc H, mask H*PW (u64), cls/cnt/mixed 3H ints (mixed padded to
-  // even), GJK simplex 18, statistics 5
-  P.wave_doubles = 4 * H + H * P.PW + H + (H + (H & 1)) / 2 + 18 + 5;
-  const int budget = 160 * 1024 / 8;
-  int waves = (budget - off) / P.wave_doubles;
-  if (waves > LQRO_PAIR_LB / 64) waves = LQRO_PAIR_LB / 64;
-  if (waves < 1) {
+  P.obs_jj = INT_MAX;   // (no obstacle columns)
+  int lds_bytes = 0;
+  if (!pair_layout(g, false, P, lds_bytes)) {
     fprintf(stderr, "liblqro: horizon %d x %d points does not fit in LDS\n", H, NP);
     delete c;
     return LQRO_E_ARG;
   }
-  P.waves = waves;
-  P.max_waves = waves;
-  off += waves * P.wave_doubles;
-  c->lds_bytes = off * 8;
+  c->lds_bytes = lds_bytes;
   int rc = ctx_alloc(c);
   if (rc) { lqro_destroy(c); return rc; }
   std::vector<double> S(3 * (size_t)NP);
   lqro_sphere(NP, g.xy_radius, g.z_radius, S.data());
-  // max |u_p| with s_p = diag(2r_xy, 2r_xy, 2r_z) u_p (createSpheres, :743-745)
   {
     const double rad[3] = {2 * g.xy_radius, 2 * g.xy_radius, 2 * g.z_radius};
-    double um = 0.0;
-    for (int p = 0; p < NP; ++p) {
-      double u2 = 0.0;
-      for (int d = 0; d < 3; ++d) { const double u = S[3 * p + d] / rad[d]; u2 += u * u; }
-      um = std::max(um, std::sqrt(u2));
-    }
-    c->umax = um * (1.0 + 1e-12);
+    c->umax = sphere_umax(S.data(), NP, rad);
     P.rad0 = rad[0]; P.rad1 = rad[1]; P.rad2 = rad[2]; P.umax = c->umax;
   }
   {
@@ -234,9 +317,7 @@ int lqro_create(const lqro_config* cfg, lqro_ctx** out) {
     lqro_destroy(c);
     return LQRO_E_HIP;
   }
-  const bool attr_ok = pair_set_lds_t<16, false>(c->lds_bytes) && pair_set_lds_t<16, true>(c->lds_bytes) &&
-                       pair_set_lds_t<12, false>(c->lds_bytes) && pair_set_lds_t<12, true>(c->lds_bytes);
-  if (!attr_ok) {
+  if (!pair_set_lds(c->lds_bytes)) {
     lqro_destroy(c);
     return LQRO_E_HIP;
   }
@@ -366,6 +447,96 @@ int lqro_set_fence(lqro_ctx* c, const double* lo, const double* hi, double tau) 
   return LQRO_OK;
 }
 
+// lqro_set_obstacles / _device.  own: `states` is a host array to copy.
+static int set_obstacles(lqro_ctx* c, const double* states, int M, double oxy, double oz, double resp, bool own) {
+  if (!c) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;   // the pending half-step's tail still reads the slots
+  const lqro_config& g = c->cfg;
+  if (M <= 0 || !states) M = 0;
+  if (M > 0) {
+    if (!(oxy >= 0) || !(oz >= 0) || !std::isfinite(oxy) || !std::isfinite(oz) || !(resp > 0 && resp <= 1))
+      return LQRO_E_ARG;
+    if ((long long)c->nrows * ((long long)g.n_agents - 1 + M) > (long long)INT_MAX) return LQRO_E_ARG;   // (slots are ints)
+  }
+  if (int rc = ctx_enter(c, false)) return rc;
+  const size_t N = g.n_agents, X = g.x_dim, H = g.horizon, NP = g.n_points;
+  // the obstacle columns' sphere: createSpheres over the summed radii; the
+  // agents' tables serve when it is theirs bit for bit
+  std::vector<double> So;
+  bool shape = false;
+  if (M > 0) {
+    std::vector<double> S(3 * NP);
+    So.resize(3 * NP);
+    lqro_sphere((int)NP, g.xy_radius, g.z_radius, S.data());
+    sphere_axes((int)NP, g.xy_radius + oxy, g.z_radius + oz, So.data());
+    shape = memcmp(S.data(), So.data(), sizeof(double) * So.size()) != 0;
+  }
+  PairArgs pa = c->pa;
+  int lds_bytes = 0;
+  if (!pair_layout(g, shape, pa, lds_bytes)) return LQRO_E_ARG;   // (H x NP leaves no room for a second sphere)
+  // every new buffer first: a failed call leaves the context as it was
+  const int npr = (int)N - 1 + M;
+  double *cols = nullptr, *copy = nullptr, *dSo = nullptr, *dRo = nullptr;
+  SlotBufs sb{};
+  int rc = LQRO_OK;
+  if (M > 0 && c->mem.get(cols, (N + M) * X)) rc = LQRO_E_NOMEM;
+  if (!rc && M > 0 && own && c->mem.get(copy, (size_t)M * X)) rc = LQRO_E_NOMEM;
+  if (!rc && shape && (c->mem.get(dSo, 3 * NP) || c->mem.get(dRo, N * H))) rc = LQRO_E_NOMEM;
+  if (!rc && npr != c->npr) rc = slots_alloc(c, npr, sb);
+  if (!rc && copy && hipMemcpy(copy, states, sizeof(double) * M * X, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  if (!rc && shape && hipMemcpy(dSo, So.data(), sizeof(double) * So.size(), hipMemcpyHostToDevice) != hipSuccess)
+    rc = LQRO_E_HIP;
+  if (!rc && !pair_set_lds(lds_bytes)) rc = LQRO_E_HIP;
+  if (rc) {
+    c->mem.release(cols); c->mem.release(copy); c->mem.release(dSo); c->mem.release(dRo);
+    slots_release(c, sb);
+    (void)pair_set_lds(c->lds_bytes);
+    return rc;
+  }
+  if (npr != c->npr) {
+    // every slot number kept across steps is void: the last step's
+    // inside-hull list (prevn = 0), the hot and speculation marks (the new
+    // buffer is zeroed), the rows' counters; the schedule starts over as in
+    // a new context.  The carried normal stays.
+    slots_adopt(c, npr, sb);
+    if (c->d_hot2) HIPCHK(hipMemset(c->d_hot2, 0, sizeof(int) * LQRO_H2_WORDS));
+    HIPCHK(hipMemset(c->d_rowpend, 0, sizeof(int) * 2 * (size_t)c->nrows));
+    for (int k = 0; k < 2; ++k) c->h_feedback[k] = kNoFeedback;
+    c->nstep = 0;
+  }
+  c->mem.release(c->d_cols); c->mem.release(c->d_obsown); c->mem.release(c->d_So); c->mem.release(c->d_Ro);
+  c->d_cols = cols; c->d_obsown = copy; c->d_So = dSo; c->d_Ro = dRo;
+  c->d_obs = M > 0 ? (own ? copy : states) : nullptr;
+  c->nobs = M;
+  c->obs_resp = M > 0 ? resp : 0.0;
+  c->obs_shape = shape ? 1 : 0;
+  pa.orad0 = pa.orad1 = shape ? g.xy_radius + oxy : pa.rad0;
+  pa.orad2 = shape ? g.z_radius + oz : pa.rad2;
+  pa.oumax = pa.umax;
+  if (shape) {
+    const double rad[3] = {pa.orad0, pa.orad1, pa.orad2};
+    pa.oumax = sphere_umax(So.data(), (int)NP, rad);
+  }
+  c->pa = pa;
+  c->lds_bytes = lds_bytes;
+  if (shape && c->have_gains) {   // (else lqro_set_gains builds it with its tables)
+    LAUNCH(launch_obs_rtab(c->stream, c->per_agent ? (int)N : 1, (int)H, c->d_T, c->d_Ro, pa.orad0, pa.orad1, pa.orad2,
+                           pa.oumax));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return LQRO_OK;
+}
+
+int lqro_set_obstacles(lqro_ctx* c, const double* states, int32_t n_obstacles, double obs_xy_radius,
+                       double obs_z_radius, double responsibility) {
+  return set_obstacles(c, states, n_obstacles, obs_xy_radius, obs_z_radius, responsibility, true);
+}
+
+int lqro_set_obstacles_device(lqro_ctx* c, const double* d_states, int32_t n_obstacles, double obs_xy_radius,
+                              double obs_z_radius, double responsibility) {
+  return set_obstacles(c, d_states, n_obstacles, obs_xy_radius, obs_z_radius, responsibility, false);
+}
+
 int lqro_set_gains(lqro_ctx* c, const double* A, const double* B, const double* L,
                    const double* E, int32_t per_agent) {
   if (!c || !A || !B || !L || !E) return LQRO_E_ARG;
@@ -381,6 +552,9 @@ int lqro_set_gains(lqro_ctx* c, const double* A, const double* B, const double* 
   HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
   LAUNCH(launch_tables(c->stream, (int)na, (int)X, (int)U, g.horizon, c->d_A, c->d_B, c->d_L, c->d_E, per_agent ? 1 : 0,
                        c->d_T, c->d_NCF, c->d_R, c->d_TF, c->pa.rad0, c->pa.rad1, c->pa.rad2, c->umax, c->d_err));
+  if (c->obs_shape)
+    LAUNCH(launch_obs_rtab(c->stream, (int)na, g.horizon, c->d_T, c->d_Ro, c->pa.orad0, c->pa.orad1, c->pa.orad2,
+                           c->pa.oumax));
   int err = 0;
   HIPCHK(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -407,7 +581,7 @@ static LpArgs lp_args(const lqro_ctx* c, int npr, const double* d_vgoal, double*
 // (d_lpnv: where an early LP would write, d_newv: the caller's buffer)
 static StepShape step_shape(const lqro_ctx* c, int phase, const double* d_lpnv, const double* d_newv) {
   StepShape S{};
-  S.n_cu = c->n_cu; S.nrows = c->nrows; S.npr = c->npr; S.nbr_k = c->nbr_k;
+  S.n_cu = c->n_cu; S.nrows = c->nrows; S.npr = c->npr - c->nobs; S.n_obs = c->nobs; S.nbr_k = c->nbr_k;
   S.hnp = (size_t)c->cfg.horizon * c->cfg.n_points;
   S.per_agent = c->per_agent; S.qhull_order = c->qhull_order; S.phase = phase;
   S.has_newv = d_lpnv != nullptr; S.newv_is_callers = d_lpnv == d_newv;
@@ -424,7 +598,11 @@ static StepShape step_shape(const lqro_ctx* c, int phase, const double* d_lpnv, 
 static PairArgs pair_args(const lqro_ctx* c, const StepPlan& plan, const double* d_x) {
   const lqro_config& g = c->cfg;
   PairArgs P = c->pa;   // (the LDS layout and the sphere's bounds; the rest zero: no hot list)
-  P.N = g.n_agents; P.H = g.horizon; P.NP = g.n_points; P.min_reach = g.min_reach;
+  P.N = g.n_agents + c->nobs; P.H = g.horizon; P.NP = g.n_points; P.min_reach = g.min_reach;
+  if (c->nobs > 0) {   // (d_x: the context's column array; else obs_jj stays INT_MAX)
+    P.obs_jj = g.n_agents - 1; P.obs_resp = c->obs_resp;
+    P.So = c->obs_shape ? c->d_So : c->d_S; P.Ro = c->obs_shape ? c->d_Ro : c->d_R;
+  }
   P.row_begin = c->rb; P.row_stride = c->rs; P.nrows = c->nrows; P.npr = plan.npr;
   P.per_agent = c->per_agent;
   P.vmax = g.vmax_reach;
@@ -486,7 +664,8 @@ static HullArgs hull_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
                           double* d_lpnv) {
   const lqro_config& g = c->cfg;
   HullArgs Hh{};   // (block 0's scratch, no external points: zero)
-  Hh.N = g.n_agents; Hh.X = g.x_dim; Hh.H = g.horizon; Hh.NP = g.n_points;
+  Hh.N = g.n_agents + c->nobs; Hh.X = g.x_dim; Hh.H = g.horizon; Hh.NP = g.n_points;
+  if (c->nobs > 0) { Hh.So = P.So; Hh.obs_jj = P.obs_jj; Hh.obs_resp = P.obs_resp; }
   Hh.row_begin = c->rb; Hh.row_stride = c->rs; Hh.npr = plan.npr; Hh.per_agent = c->per_agent;
   Hh.nbr_list = P.nbr_list;
   Hh.r2 = P.r2; Hh.r2_lo = P.r2_lo; Hh.r2_hi = P.r2_hi;
@@ -521,6 +700,16 @@ static HullArgs hull_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
   return Hh;
 }
 
+// the obstacle columns among a row's slots, for k_stale / k_stale_rows
+static ObsSlots obs_slots(const lqro_ctx* c) {
+  ObsSlots O{};
+  if (c->nobs > 0) {
+    O.on = c->d_cols; O.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;
+    O.jj = c->cfg.n_agents - 1; O.resp = c->obs_resp;
+  }
+  return O;
+}
+
 // speculative builds: the marks, and the ticket over the jobs k_prio_prev queued
 static HullArgs with_spec(const lqro_ctx* c, HullArgs H) {
   H.spec_mark = c->d_hotmark; H.spec_n = c->d_hot2 + LQRO_H2_SPEC; H.spec_next = c->d_hot2 + LQRO_H2_SPEC_NEXT;
@@ -535,7 +724,7 @@ static HullArgs handed_over(const lqro_ctx* c, HullArgs H) {
 
 // The step's first launches on the caller's stream: behind the last step, the
 // counters and queues reset, the neighbour lists, the hot list.
-static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, hipStream_t s) {
+static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, const double* d_x, hipStream_t s) {
   const lqro_config& g = c->cfg;
   // the context's scratch (queues, counters, plane slots, tables) is reused by
   // every step: a step enqueued on another stream than the last one, or a
@@ -545,11 +734,14 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
   HIPCHK(hipMemsetAsync(c->d_hcount, 0, sizeof(int) * LQRO_HC_WORDS, s));
   HIPCHK(hipMemsetAsync(c->d_stats, 0, sizeof(unsigned long long) * LQRO_ST_WORDS, s));
   HIPCHK(hipMemsetAsync(c->d_hq, 0xFF, sizeof(int) * (size_t)c->hull_cap, s));
+  // obstacles: this step's columns (P.x), the caller's agents then the obstacles
+  if (c->nobs > 0)
+    LAUNCH(launch_cols(s, d_x, (size_t)g.n_agents * g.x_dim, c->d_obs, (size_t)c->nobs * g.x_dim, c->d_cols));
   // Qhull order: the normal the last step's last eligible pair left enters this step
   if (c->qhull_order)
     HIPCHK(hipMemcpyAsync(c->d_carry, c->d_carry + 3, sizeof(double) * 3, hipMemcpyDeviceToDevice, s));
   if (c->nbr_k > 0) {
-    LAUNCH(hipLaunchKernelGGL(k_nbr, dim3((unsigned)c->nrows), dim3(64), 0, s, P.x, g.x_dim, g.n_agents, c->rb, c->rs,
+    LAUNCH(hipLaunchKernelGGL(k_nbr, dim3((unsigned)c->nrows), dim3(64), 0, s, P.x, g.x_dim, g.n_agents + c->nobs, c->rb, c->rs,
                               c->npr, c->nbr_r2, c->nbr_k, plan.npr, c->d_nbrlist, c->d_stats));
   }
   if (plan.early) HIPCHK(hipMemsetAsync(c->d_rowpend, 0, sizeof(int) * 2 * (size_t)c->nrows, s));
@@ -649,7 +841,7 @@ static int enqueue_hulls_after_sweep(lqro_ctx* c, const StepPlan& plan, const Hu
                               plan.split ? c->d_hotmark : nullptr, plan.slots));
     if (phase == 0) {
       LAUNCH(launch_stale(s, c->d_planes, c->d_qnrm, c->d_qstale, c->d_hcount + LQRO_HC_FACET0, c->hull_cap, Hh.x, g.x_dim,
-                          plan.npr, c->rb, c->rs, c->d_carry, c->d_recs, plan.slots));
+                          plan.npr, c->rb, c->rs, c->d_carry, c->d_recs, plan.slots, obs_slots(c)));
     }
     return LQRO_OK;
   }
@@ -672,7 +864,7 @@ static int enqueue_tail(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   const int slot = (int)(c->nstep & 1);
   if (d_rowtab && c->qhull_order) {
     LAUNCH(launch_stale_rows(s, c->d_planes, c->d_qnrm, c->d_qstale, c->d_hcount + LQRO_HC_FACET0, c->hull_cap, d_x, g.x_dim, npr,
-                             c->rb, c->rs, d_rowtab, g.n_agents, c->d_carry, c->d_recs, slots));
+                             c->rb, c->rs, d_rowtab, g.n_agents, c->d_carry, c->d_recs, slots, obs_slots(c)));
   }
   c->pending = 0;
   LpArgs La = lp_args(c, npr, d_vgoal, d_newv);
@@ -736,10 +928,10 @@ static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   c->early_step = plan.early ? 1 : 0;
   c->early_internal = plan.early_internal ? 1 : 0;
   // 2. the kernels' arguments
-  const PairArgs P = pair_args(c, plan, d_x);
+  const PairArgs P = pair_args(c, plan, c->nobs > 0 ? c->d_cols : d_x);   // (k_cols fills d_cols in the prologue)
   const HullArgs Hh = hull_args(c, plan, P, d_vgoal, d_lpnv);
   // 3. the launches
-  if (int rc = enqueue_prologue(c, plan, P, s)) return rc;
+  if (int rc = enqueue_prologue(c, plan, P, d_x, s)) return rc;
   // the row launch is submitted before the side stream's work: should the two
   // streams land on one hardware queue (a second context in the process), the
   // main grid still runs first on its CUs instead of k_side's row tail

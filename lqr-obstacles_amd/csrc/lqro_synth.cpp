@@ -21,19 +21,27 @@ extern "C" void lqro_model_default(lqro_model* m) {
   m->pos_weight = 0.05;
 }
 
-extern "C" int lqro_sphere(int32_t np, double xy_radius, double z_radius, double* out) {
-  if (np <= 0 || !out) return LQRO_E_ARG;
+// createSpheres (LQRO:735-750) over its two semi-axes (the reference's
+// 2*XYRADIUS and 2*ZRADIUS; lqro_set_obstacles: the sums of LQRO:752-767's kind)
+namespace lqro {
+void sphere_axes(int np, double axy, double az, double* out) {
   double dlong = M_PI * (3.0 - std::sqrt(5.0));
   double dz = 2.0 / np;
   double lon = 0;
   double z = 1.0 - dz / 2.0;
   for (int i = 0; i < np; i++) {
-    out[3 * i + 0] = 2 * xy_radius * std::cos(lon) * std::sqrt(1 - z * z);
-    out[3 * i + 1] = 2 * xy_radius * std::sin(lon) * std::sqrt(1 - z * z);
-    out[3 * i + 2] = 2 * z_radius * z;
+    out[3 * i + 0] = axy * std::cos(lon) * std::sqrt(1 - z * z);
+    out[3 * i + 1] = axy * std::sin(lon) * std::sqrt(1 - z * z);
+    out[3 * i + 2] = az * z;
     z -= dz;
     lon += dlong;
   }
+}
+}  // namespace lqro
+
+extern "C" int lqro_sphere(int32_t np, double xy_radius, double z_radius, double* out) {
+  if (np <= 0 || !out) return LQRO_E_ARG;
+  lqro::sphere_axes(np, 2 * xy_radius, 2 * z_radius, out);
   return LQRO_OK;
 }
 

@@ -86,6 +86,7 @@ EXPORTS = (
     "lqro_step_device_begin", "lqro_step_device_end",
     "lqro_get_stats_ex", "lqro_get_hull_failures", "lqro_get_hull_builds", "lqro_get_qhmerge_pairs",
     "lqro_set_user_planes", "lqro_set_user_planes_device", "lqro_set_fence",
+    "lqro_set_obstacles", "lqro_set_obstacles_device",
 )
 
 NORMALS_PER_AGENT = 22   # LQRO_NORMALS_PER_AGENT: 16 propagate + 6 observation
@@ -140,6 +141,9 @@ def lib() -> C.CDLL:
         L.lqro_set_user_planes.argtypes = [vp, vp, vp]
         L.lqro_set_user_planes_device.argtypes = [vp, vp, i32, vp]
         L.lqro_set_fence.argtypes = [vp, vp, vp, dbl]
+        if hasattr(L, "lqro_set_obstacles"):   # (older libraries in A/B runs lack them)
+            L.lqro_set_obstacles.argtypes = [vp, vp, i32, dbl, dbl, dbl]
+            L.lqro_set_obstacles_device.argtypes = [vp, vp, i32, dbl, dbl, dbl]
         L.lqro_set_carry_normal.argtypes = [vp, vp]
         L.lqro_get_carry_normal.argtypes = [vp, vp]
         _lib = L
@@ -271,6 +275,8 @@ class Context:
             re = cfg.n_agents
         self.rows = (rb, re)
         self.row_ids = np.arange(rb, re, max(cfg.row_stride, 1))   # the agents whose rows this computes
+        self.n_obstacles = 0
+        self._obs_keep = None      # a device tensor given to set_obstacles, kept alive
 
     def close(self):
         if self._h:
@@ -331,6 +337,41 @@ class Context:
         lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (3,)))
         hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (3,)))
         _check(lib().lqro_set_fence(self._h, _p(lo), _p(hi), float(tau)), "lqro_set_fence")
+
+    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility: float = 1.0):
+        """Obstacles: M columns of every row's pair loop that are not agents
+        (lqro_set_obstacles; the reference's commented floor block,
+        LQRO:1377-1379, 1421-1434, 752-767).  states: (M, x_dim) — a numpy
+        array (copied), or a float64 torch tensor on the context's device,
+        read when each step runs (rewrite it on the step's stream before the
+        step: obstacles that move); obstacle_states() builds hover-trim ones.
+        None or M = 0 clears.  xy_radius / z_radius: the obstacles' ellipsoid
+        (default: the agents'; (0, 0): a point); responsibility in (0, 1]
+        replaces the 0.5 of LQRO:1416 for an obstacle column (1.0: the agent
+        does all the avoiding).  A row then has n_agents - 1 + M records, the
+        obstacle ones with j = n_agents + o.  Changes results against the
+        reference."""
+        oxy = self.cfg.xy_radius if xy_radius is None else float(xy_radius)
+        oz = self.cfg.z_radius if z_radius is None else float(z_radius)
+        X = self.cfg.x_dim
+        if states is None:
+            _check(lib().lqro_set_obstacles(self._h, None, 0, oxy, oz, float(responsibility)), "lqro_set_obstacles")
+            self.n_obstacles, self._obs_keep = 0, None
+            return
+        if isinstance(states, np.ndarray) or not hasattr(states, "data_ptr"):
+            st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, X)
+            _check(lib().lqro_set_obstacles(self._h, _p(st), st.shape[0], oxy, oz, float(responsibility)),
+                   "lqro_set_obstacles")
+            self.n_obstacles, self._obs_keep = st.shape[0], None
+            return
+        import torch
+        if states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous() or \
+                states.dim() != 2 or states.shape[1] != X:
+            raise LqroError(f"set_obstacles: need a contiguous float64 device tensor (M, {X})")
+        m = int(states.shape[0])
+        _check(lib().lqro_set_obstacles_device(self._h, C.c_void_p(states.data_ptr() if m else None), m, oxy, oz,
+                                               float(responsibility)), "lqro_set_obstacles_device")
+        self.n_obstacles, self._obs_keep = m, (states if m else None)
 
     def set_gains(self, A, B, L, E, per_agent: bool = False):
         A, B, L, E = (np.ascontiguousarray(v, dtype=np.float64) for v in (A, B, L, E))
@@ -402,7 +443,7 @@ class Context:
                                           C.c_void_p(stream or None)), "lqro_step_device_end")
 
     def records(self) -> np.ndarray:
-        n = len(self.row_ids) * (self.cfg.n_agents - 1)
+        n = len(self.row_ids) * (self.cfg.n_agents - 1 + self.n_obstacles)
         out = np.zeros(n, dtype=RECORD_DTYPE)
         got = C.c_int64()
         _check(lib().lqro_get_records(self._h, _p(out), n, C.byref(got)), "lqro_get_records")
@@ -525,6 +566,21 @@ def synthetic_swarm(n: int, x_dim: int = 16, seed: int = SEED, box: float | None
         for k in range(3):
             vg[i, k] = 2.0 * next(g) - 1.0
     return x, vg
+
+
+def obstacle_states(pos, vel=None, x_dim: int = 16) -> np.ndarray:
+    """Hover-trim states for Context.set_obstacles: zeros, then position
+    [0..2] and velocity [3..5] (default 0: a static obstacle), and for x_dim =
+    16 the rotor forces at nominalInput (LQRO:188), as synthetic_swarm has
+    them — so that x_i - x_o is a position / velocity difference only."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    st = np.zeros((pos.shape[0], x_dim))
+    st[:, 0:3] = pos
+    if vel is not None:
+        st[:, 3:6] = np.asarray(vel, dtype=np.float64).reshape(-1, 3)
+    if x_dim == 16:
+        st[:, 12:16] = 9.80665 * 0.500 / 4
+    return st
 
 
 def swap_scenario():
@@ -669,6 +725,11 @@ class Simulator:
         else:
             self.ctx.set_gains(self.A, self.B, Ls[0], Es[0])
         return g
+
+    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility: float = 1.0):
+        """Bodies that are not in qlist as extra columns of every agent's pair
+        loop (Context.set_obstacles); None clears."""
+        self.ctx.set_obstacles(states, xy_radius, z_radius, responsibility)
 
     def step(self):
         x = np.stack([q.x for q in self.qlist])
@@ -829,7 +890,7 @@ class DeviceLoop:
     def __init__(self, x0, vgoal0, gains: dict, horizon: int, n_points: int = 100, *,
                  p_goal=None, rank: int = 0, world: int = 1, dist=None, device=None,
                  model: Model | None = None, seed: int = 1, stream=None, rows: str = "block",
-                 flags: int = LQRO_FLAG_QHULL_ORDER, fence=None, user_planes=None):
+                 flags: int = LQRO_FLAG_QHULL_ORDER, fence=None, user_planes=None, obstacles=None):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -854,6 +915,10 @@ class DeviceLoop:
             self.ctx.set_fence(*fence)
         if user_planes is not None:
             self.ctx.set_user_planes(user_planes)
+        # obstacles = states, or (states, xy_radius, z_radius, responsibility):
+        # every rank the same set (Context.set_obstacles)
+        if obstacles is not None:
+            self.set_obstacles(*(obstacles if isinstance(obstacles, tuple) else (obstacles,)))
         self.x = torch.from_numpy(np.ascontiguousarray(x0, np.float64)).to(self.dev)
         self.vgoal = torch.from_numpy(np.ascontiguousarray(vgoal0, np.float64)).to(self.dev)
         self.newv = torch.zeros((n, 3), **f64)
@@ -878,6 +943,11 @@ class DeviceLoop:
 
     def _sid(self):
         return self.stream.cuda_stream
+
+    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility: float = 1.0):
+        """This rank's context takes the obstacle set (every rank the same
+        arguments); a device tensor is read by every later step."""
+        self.ctx.set_obstacles(states, xy_radius, z_radius, responsibility)
 
     def step(self, gather: bool = False):
         """The pair loop for the own rows; newV of the own rows on the device
