@@ -34,7 +34,9 @@ struct StepKnobs {
   int qhull_inline;          // LQRO_QHULL_INLINE_BIG: k_qhull rebuilds a capped build in place (default 1)
   int qhull_big;             // LQRO_QHULL_BIG=1: every pair in k_qhull_big (A/B runs)
   int qhull_flags;           // LQRO_QHULL_FLAGS: k_qhull's helper waves (1), emit lane state (2), queue pre-scan (4),
-                             // a long emit over the waves (16); default 23
+                             // a long emit over the waves (16), no event for a trigger without sharp new
+                             // facets (32), helpers posted under the state a sharp trigger leads to (64);
+                             // default 119
   int hull_big_only;         // LQRO_HULL_BIG: skip the LDS hull (A/B)
   int local_hull;            // LQRO_LOCAL_HULL (default 1): k_lhull first, k_hull for what it hands over
   int lhull_prof;            // LQRO_LHULL_PROFILE: k_lhull writes its per-job words
@@ -84,7 +86,7 @@ inline StepKnobs knobs_from_env(int n_cu) {
   // a build past k_qhull's caps rebuilt at once on its CU (q3_big_inline)
   // instead of in the k_qhull_big launch after the sweep
   k.qhull_inline = env_int("LQRO_QHULL_INLINE_BIG", 1) != 0;
-  k.qhull_flags = env_int("LQRO_QHULL_FLAGS", 23);
+  k.qhull_flags = env_int("LQRO_QHULL_FLAGS", 119);
   // the side's width from the measured work of the step two before (the
   // sweep's CU time, the builds' total and longest): no wider than leaves
   // the sweep no longer than the builds (LQRO_QHULL_BALANCE=0: one CU per

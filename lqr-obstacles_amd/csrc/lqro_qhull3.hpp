@@ -892,12 +892,23 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
   // 0 under its current state, posted from `from` on; an event (a state
   // change) stops them and posts the rest again under the new state
   const bool help = np > 64 && (L.qflags & 1);
+  // Without sharp new facets the findbest_notsharp trigger changes no point's
+  // path (q3_locate: it only spares Qhull a second qh_sharpnewfacets), so the
+  // sequence starts with it set: no event, no second locate of a chunk's tail
+  if (sharp == 0 && !init && (L.qflags & 32)) S.notsharp = 1;
+  // With sharp new facets the trigger (nearly always in the first chunk)
+  // switches the state to findbestnew: the helpers are posted under that
+  // state from the start.  Wave 0 locates in order under its own state until
+  // the trigger fires, and takes the helpers' chunks only from then on
+  const bool a2 = help && sharp == 1 && (L.qflags & 64);
+  bool ahead = false;   // the current post's state is the one the trigger leads to
   const Q3Col C0 = q3_col0(L, lane);
   auto post = [&](int from2) {   // (no helper holds a claim: hctl = 0, hbusy = 0)
     S.hgen = S.hgen % 32767 + 1;
+    ahead = a2 && !S.findbestnew;
     if (lane == 0) {
       L.hq_end = (np + 63) >> 6; L.hq_from = from2; L.hq_np = np; L.hq_sharp = sharp; L.hq_init = init ? 1 : 0;
-      L.hq_findbestnew = S.findbestnew; L.hq_notsharp = S.notsharp; L.hq_nnew = S.nnew; L.hq_nmov = S.nmov;
+      L.hq_findbestnew = ahead ? 1 : S.findbestnew; L.hq_notsharp = S.notsharp; L.hq_nnew = S.nnew; L.hq_nmov = S.nmov;
       L.hq_nvis = S.nvis; L.hq_max_outside = S.max_outside;
       L.hcons = from2 >> 6;
       for (int b = 0; b < Q3_HR; b++) L.hr_st[b] = 0;
@@ -919,11 +930,15 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
     if (b != 0) S.status |= QHS_CAPACITY | QHS_TIMEOUT;
   };
   int from = 0;
+  bool posted = false;   // the helpers' post stands (the trigger under `ahead`): wave 0 goes on in its own chunk
   while (from < np && !(S.status & QHS_CAPACITY)) {
     int ev_pos = np, ev_kind = 0, ev_dst = -1;
     double ev_d = 0.0;
-    if (help) post(from);
-    bool first = help;   // (the posted sequence's first chunk: claimed by the post)
+    if (help && !posted) post(from);
+    // (the posted sequence's first chunk: claimed by the post; after the
+    // trigger under `ahead`: the rest of the chunk wave 0 located, if any)
+    bool first = help && (!posted || (from & 63) != 0);
+    posted = false;
     for (int c = from & ~63; c < np; c += 64) {
       Q3C(23, 1);
       const int pos = c + lane;
@@ -933,11 +948,17 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
       HullPt pt = pre;
       int f = -1, isout = 0, trig = 0;
       bool mine = !help || first;
+      // (the helpers' chunks are under the state to come: wave 0 locates this
+      // one itself; a helper that holds it answers before its buffer moves on)
+      const bool own = ahead && !S.findbestnew;
+      int held = -1;
       if (help && !first) {
         // this chunk's results from a helper, or claimed and located here
         const int k = c >> 6, b = k % Q3_HR;
         int st = q3_ld_acq(&L.hr_st[b]);
-        if (st != k + 1) {
+        if (own && st == k + 1) {
+          mine = true;   // (answered already, and not used)
+        } else if (st != k + 1) {
           int m = 0;
           if (lane == 0) {
             unsigned e = __hip_atomic_load(&L.hctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -949,6 +970,7 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
 #ifdef LQRO_QHULL_LONGPROF
           const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
 #endif
+          if (!mine && own) { mine = true; held = b; }
           if (!mine) st = q3_wait(&L.hr_st[b], k + 1, false);
 #ifdef LQRO_QHULL_LONGPROF
           if (!mine) S.pf.lp_hwait += __builtin_amdgcn_s_memrealtime() - tw0;
@@ -986,6 +1008,10 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
         if (trig) kind |= 1;
       }
       S.status |= qh_wave_or(ls);
+      if (held >= 0 && q3_wait(&L.hr_st[held], (c >> 6) + 1, false) != (c >> 6) + 1) {
+        S.status |= QHS_CAPACITY | QHS_TIMEOUT;
+        break;
+      }
       if (help && lane == 0) q3_st_rel_lds(&L.hcons, (c >> 6) + 1);   // (its buffer is read)
       const unsigned long long b = __ballot(kind != 0);
       const int last = b ? __ffsll((long long)b) - 1 : 63;   // positions up to c+last are final
@@ -1031,6 +1057,15 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
         ev_d = hl_rl(d, last);
         break;
       }
+    }
+    if (ahead && !S.findbestnew && ev_kind == 1 && ev_pos + 1 < np) {
+      // the trigger alone: the state the helpers were posted under begins.
+      // No stop and no post; wave 0 locates the rest of this chunk again
+      Q3C(24, 1);
+      S.findbestnew = 1;
+      from = ev_pos + 1;
+      posted = true;
+      continue;
     }
 #ifdef LQRO_QHULL_LONGPROF
     const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
