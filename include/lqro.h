@@ -209,7 +209,8 @@ int lqro_set_neighbors(lqro_ctx* ctx, double neighbor_dist, int32_t max_neighbor
  * calculateNewV (LQRO:1223-1234) runs over that list unchanged.  A velocity
  * v satisfies a plane when normal.(v - point) >= 0, in the agent's absolute
  * velocity space (the LP's own convention, LQRO:1083).  Extra planes are as
- * soft as every other plane (linearProgram4 relaxes them like the rest);
+ * soft as every other plane (linearProgram4 relaxes them like the rest)
+ * unless lqro_set_hard_planes below makes them hard;
  * inputs must be finite.  Pair records, stats, the hull queue and the
  * carried normal do not see them.  All arrays are indexed by the global
  * agent id, so every row shard takes the same arrays and reads its own rows.
@@ -302,6 +303,53 @@ int lqro_set_obstacles_device(lqro_ctx* ctx, const double* d_states /* M*X, read
                               int32_t n_obstacles, double obs_xy_radius, double obs_z_radius,
                               double responsibility);
 
+/* ---- hard planes: constraints linearProgram4 does not relax ------------
+ * The fence, user and obstacle planes above are as soft as the pair planes:
+ * once a row's list is infeasible, linearProgram4 (LQRO:1160-1206) gives way
+ * on all of them alike.  RVO2 keeps its obstacle lines out of that
+ * relaxation: its 2-D linearProgram3(lines, numObstLines, beginLine, ..)
+ * copies the first numObstLines lines into every projected list as they are
+ * and projects only the agent lines.  lqro_set_hard_planes carries that rule
+ * to this LP.  The levels form a ladder, so the hard planes are always a
+ * prefix of row i's list, n_hard of them:
+ *   LQRO_HARD_NONE      none (the default: the step is as without this call)
+ *   LQRO_HARD_FENCE     the row's fence planes
+ *   LQRO_HARD_HEAD      its fence planes, then its live user planes
+ *   LQRO_HARD_OBSTACLES fence, user, then its obstacle columns' planes, which
+ *                       the LP then takes in column order o AHEAD of the
+ *                       agent planes (fence, user, obstacles, agents); with
+ *                       lqro_set_neighbors the obstacle slots are those whose
+ *                       neighbour is a column >= n_agents, the last of the
+ *                       row's kept slots.
+ * n_hard counts the planes actually in the list (no face at infinity, the
+ * clamped user count, no obstacle column without a plane).  linearProgram3
+ * and calculateNewV are unchanged; in linearProgram4(planes, n_hard,
+ * beginPlane, radius, result), for a violated plane i >= beginPlane,
+ * projPlanes is planes[0 .. n_hard) copied as they are, followed by the
+ * projections of planes j = n_hard .. i-1 computed as before (for i < n_hard
+ * the projected part is empty and all n_hard planes are still copied, plane
+ * i included, as in RVO2); the inner linearProgram3, the restore on failure
+ * and the distance update are unchanged.  With n_hard = 0 the row's LP is the
+ * reference's in every bit and every launch.
+ * What this promises: once the hard planes and the speed sphere are feasible
+ * together and the result satisfies them, no later relaxation leaves them.
+ * What it does not: if linearProgram3 fails ON a hard plane, or the hard
+ * planes are infeasible among themselves, the result is kept as RVO2 keeps
+ * it, and nothing is guaranteed.
+ * Only the LP's view moves at LQRO_HARD_OBSTACLES: records and their order,
+ * statistics, the hull queue, the carried normal's (i, j) order and
+ * LQRO_E_HULL / LQRO_E_QHMERGE are unchanged.  The level stays when fence,
+ * user planes or obstacles are later set or cleared; every row shard takes
+ * the same level.  A level outside 0..3: LQRO_E_ARG.  LQRO_E_STATE while a
+ * lqro_step_device_begin is pending; waits for the last enqueued step before
+ * it takes effect; allocates nothing.  Results CHANGE against the reference
+ * once a row has a hard plane. */
+#define LQRO_HARD_NONE      0
+#define LQRO_HARD_FENCE     1
+#define LQRO_HARD_HEAD      2
+#define LQRO_HARD_OBSTACLES 3
+int lqro_set_hard_planes(lqro_ctx* ctx, int32_t level);
+
 /* One control step: the pair loop LQRO:1393-1436 for the context's rows.
  * x: n_agents*X agent states (Quadrotor::x), vgoal: n_agents*3,
  * newv: n_agents*3 (only rows [row_begin,row_end) are written).  Host
@@ -351,6 +399,14 @@ int lqro_step_device_end(lqro_ctx* ctx, const double* d_rowtab, double* d_newv, 
  * velocity vgoal[3r..3r+2]; writes newv[3r..3r+2].  Synchronous. */
 int lqro_calculate_new_v(const float* planes, const int64_t* offsets, int32_t n_agents,
                          const double* vgoal, double vmax_lp, double* newv, int32_t device);
+/* The same with a hard prefix per agent (lqro_set_hard_planes' rule):
+ * agent r's first n_hard[r] planes are kept out of linearProgram4's
+ * relaxation.  n_hard[r] above the agent's plane count is clamped to it; a
+ * negative value: LQRO_E_ARG; n_hard == NULL: all 0, which is
+ * lqro_calculate_new_v. */
+int lqro_calculate_new_v_hard(const float* planes, const int64_t* offsets, const int32_t* n_hard,
+                              int32_t n_agents, const double* vgoal, double vmax_lp, double* newv,
+                              int32_t device);
 
 /* LQRO_FLAG_QHULL_ORDER: the loop-carried normalVector (LQRO:1385) entering
  * the context's first row (set; 0,0,0 at creation) and leaving its last

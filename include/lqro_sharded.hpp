@@ -184,6 +184,12 @@ class ShardedSimulator {
           "lqro_set_obstacles");
   }
 
+  // Simulator::setHardPlanes for this rank's context: every rank passes the
+  // same level (lqro_set_hard_planes)
+  void setHardPlanes(int32_t level) {
+    if (ctx_) check(lqro_set_hard_planes(ctx_, level), "lqro_set_hard_planes");
+  }
+
   // One iteration of LQRO:1393-1446 for this rank's rows, then the state
   // exchange; returns the next seed of the rand() stream.  Enqueued only:
   // download() waits for it.

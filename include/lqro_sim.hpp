@@ -159,6 +159,16 @@ class Simulator {
           "lqro_set_obstacles");
   }
 
+  // Hard planes (lqro_set_hard_planes): level LQRO_HARD_FENCE keeps the fence
+  // planes out of linearProgram4's relaxation, LQRO_HARD_HEAD the user planes
+  // too, LQRO_HARD_OBSTACLES also the obstacle columns' planes, which the LP
+  // then takes ahead of the agent planes (RVO2's obstacle lines).  Once the
+  // hard planes and the speed sphere are feasible together and the result
+  // satisfies them, no later relaxation leaves them; if the hard planes are
+  // infeasible among themselves nothing is guaranteed.  LQRO_HARD_NONE (the
+  // default) is the reference's LP.
+  void setHardPlanes(int32_t level) { check(lqro_set_hard_planes(ctx_, level), "lqro_set_hard_planes"); }
+
   // The pair loop LQRO:1393-1436 on the GPU: every Quadrotor::newV.
   // LQRO_E_HULL (a pair without its half-plane) and LQRO_E_QHMERGE (a pair
   // whose winning facet qconvex's pre-merge may join: its half-plane is not

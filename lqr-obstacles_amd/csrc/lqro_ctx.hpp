@@ -37,7 +37,7 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   lqro::HullMemBig* d_hbig;
   lqro::HullWide* d_hwide;
   int* d_hbag;
-  int* d_lp4;                // k_lp_lds -> k_lp4 row list (6 ints per row)
+  int* d_lp4;                // k_lp_lds -> k_lp4 row list (8 ints per row)
   int* d_hotlist;            // k_prio: likely inside-hull pairs (slots), computed first
   int* d_prevq;              // Qhull order: the last step's inside-hull pairs (k_prio_save), hot_cap
   int* d_hot2;               // the split hot launch's counters: LQRO_H2_* (lqro_device.hpp)
@@ -97,6 +97,7 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   float* d_uown;                  // lqro_set_user_planes's copies
   int* d_ucown;
   int lp_cap;
+  int hard_level;                 // lqro_set_hard_planes: LQRO_HARD_* (0: every plane soft)
   // obstacle columns (lqro_set_obstacles[_device]): nobs states behind the
   // agents' in d_cols, the array the step's kernels then take for x (k_cols
   // fills it at the head of every step)

@@ -30,7 +30,7 @@ struct LpArgs {
   double* newv;
   unsigned long long* prof;   // LQRO_LP_PROFILE: cycles per row
   // rows whose linearProgram3 fails go to k_lp4 (null: linearProgram4 inline)
-  int* lp4_list;              // 6 ints per row: lrow, fail, m, nv.xyz (float bits)
+  int* lp4_list;              // 8 ints per row: lrow, fail, m, nv.xyz (float bits), n_hard, 0
   int* lp4_count;
   int* lp4_next;
   // early LP (lqro_hull.hpp hull_row_done): mode 1 runs the rows whose
@@ -40,6 +40,19 @@ struct LpArgs {
   int* rowclaim;
   int row_target;
   int mode;
+  // hard planes (lqro_set_hard_planes; linearProgram4 keeps a list's first
+  // n_hard planes out of its relaxation, lqro_lp.hpp w_lp4h).  hard: the
+  // level, LQRO_HARD_*: the row's fence planes (1), its live user planes too
+  // (2), and at 3 its obstacle-column planes, which are then compacted ahead
+  // of the agent planes.  A row's obstacle slots are [obs_first, npr),
+  // obs_first = n_agents - 1; with culling (nbr: per row npr neighbour jj,
+  // ascending, -1 padded) the slots whose jj >= obs_first, the suffix of its
+  // live slots.  obs_first < 0 (no obstacles, or hard < 3): slot order as it is.
+  // nhard_rows (lqro_calculate_new_v_hard): per row n_hard itself, clamped to
+  // the row's plane count; null: from the level.
+  int hard, obs_first;
+  const int* nbr;
+  const int* nhard_rows;
 };
 
 // The fence (lqro_set_fence): an axis-aligned box [lo, hi] the agents'

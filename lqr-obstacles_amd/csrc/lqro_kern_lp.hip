@@ -125,14 +125,34 @@ __device__ __forceinline__ void lp_row(const LpArgs& A, int lrow, float* planes,
                 lane);
     m0 = A.nfence + nu;
   }
-  const int m = lp_compact<PS>(A.slots + (size_t)lrow * A.npr * 8, A.npr, planes, lane, m0);
+  // the hard prefix (LpArgs::hard): fence planes, live user planes, and at
+  // level 3 the obstacle slots' planes, compacted ahead of the agent slots'
+  int n_hard = A.hard >= 2 ? m0 : A.hard == 1 ? min(A.nfence, m0) : 0;
+  const float* slots = A.slots + (size_t)lrow * A.npr * 8;
+  int m;
+  if (A.hard >= 3 && A.obs_first >= 0) {
+    int f = min(A.obs_first, A.npr);   // the row's first obstacle slot
+    if (A.nbr) {
+      f = 0;
+      for (int base = 0; base < A.npr; base += 64) {
+        const int q = base + lane;
+        const int jj = q < A.npr ? A.nbr[(size_t)lrow * A.npr + q] : -1;
+        f += __popcll(__ballot(jj >= 0 && jj < A.obs_first));
+      }
+    }
+    n_hard = lp_compact<PS>(slots + 8 * (size_t)f, A.npr - f, planes, lane, m0);
+    m = lp_compact<PS>(slots, f, planes, lane, n_hard);
+  } else {
+    m = lp_compact<PS>(slots, A.npr, planes, lane, m0);
+  }
+  if (A.nhard_rows) n_hard = min(A.nhard_rows[lrow], m);
   const v3 pref = V3((float)A.vgoal[3 * i], (float)A.vgoal[3 * i + 1], (float)A.vgoal[3 * i + 2]);
   v3 nv = V3(0.0f, 0.0f, 0.0f);
   const int fail = w_lp3<PS>(planes, m, A.vmax, pref, false, nv, lane);          // :1228
 #ifdef LQRO_LP_PROFILE
   int lp4_iters = 0;
   if (fail < m)
-    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.cap * PS, lane, lp4_iters);
+    w_lp4<PS, true>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.cap * PS, lane, lp4_iters, n_hard);
   if (lane == 0 && A.prof && lrow < 4096) A.prof[32 + 4096 + lrow] = ((unsigned long long)m << 40) |
                                                ((unsigned long long)fail << 20) | (unsigned)lp4_iters;
 #else
@@ -144,14 +164,15 @@ __device__ __forceinline__ void lp_row(const LpArgs& A, int lrow, float* planes,
       for (int q = lane; q < PS * m; q += 64) dst[q] = planes[q];
     if (lane == 0) {
       const int k = atomicAdd(A.lp4_count, 1);
-      int* e = A.lp4_list + 6 * (size_t)k;
+      int* e = A.lp4_list + 8 * (size_t)k;
       e[0] = lrow; e[1] = fail; e[2] = m;
       e[3] = __float_as_int(nv.x); e[4] = __float_as_int(nv.y); e[5] = __float_as_int(nv.z);
+      e[6] = n_hard; e[7] = 0;
     }
     return;
   }
   if (fail < m)
-    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.cap * PS, lane);  // :1230
+    w_lp4<PS, true>(planes, m, fail, (float)A.vmax, nv, A.proj + (size_t)lrow * A.cap * PS, lane, n_hard);  // :1230
 #endif
   if (lane == 0) {
     A.newv[3 * i] = nv.x;
@@ -213,8 +234,8 @@ __global__ void __launch_bounds__(64) k_lp4(LpArgs A, int proj_in_lds) {
     // these ballot-driven loops hung on gfx950; the extra workgroups exit at once)
     const int job = blockIdx.x;
     if (job >= *A.lp4_count) return;
-    const int* e = A.lp4_list + 6 * (size_t)job;
-    const int lrow = e[0], fail = e[1], m = e[2];
+    const int* e = A.lp4_list + 8 * (size_t)job;
+    const int lrow = e[0], fail = e[1], m = e[2], n_hard = e[6];
     float* proj = proj_in_lds ? lp4_sm + (size_t)A.cap * PS : A.proj + (size_t)lrow * A.cap * PS;
     v3 nv = V3(__int_as_float(e[3]), __int_as_float(e[4]), __int_as_float(e[5]));
     const float* src = A.compact + (size_t)lrow * A.cap * 8;
@@ -224,9 +245,9 @@ __global__ void __launch_bounds__(64) k_lp4(LpArgs A, int proj_in_lds) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 #ifdef LQRO_LP_PROFILE
     int lp4_iters = 0;
-    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, proj, lane, lp4_iters);  // :1230
+    w_lp4<PS, true>(planes, m, fail, (float)A.vmax, nv, proj, lane, lp4_iters, n_hard);  // :1230
 #else
-    w_lp4<PS>(planes, m, fail, (float)A.vmax, nv, proj, lane);              // :1230
+    w_lp4<PS, true>(planes, m, fail, (float)A.vmax, nv, proj, lane, n_hard);              // :1230
 #endif
     if (lane == 0) {
       const int i = A.row_begin + lrow * A.row_stride;

@@ -293,14 +293,23 @@ __device__ __forceinline__ int w_lp3(const float* planes, int m, double radius, 
 
 // linearProgram4 (LQRO:1131-1206): the projected planes of plane i are built
 // in parallel and compacted in j order (skipped same-direction parallels keep
-// their order)
-template <int PS>
+// their order).
+// HARD: the list's first n_hard (<= m) planes are hard, RVO2's obstacle lines
+// (linearProgram3(lines, numObstLines, beginLine, ..) of its 2-D Agent.cpp)
+// carried to three dimensions: they enter every violated plane's projected
+// list as they are, one plane a lane ahead of the projections, and only
+// planes j = n_hard .. i-1 are projected.  For i < n_hard the projected part
+// is empty and all n_hard planes are still copied, plane i included, as in
+// RVO2.  The list holds max(n_hard, i) <= m planes at most, so `proj` (m
+// planes) is large enough whatever n_hard.  Without HARD (k_qhull's in-place
+// LP, lqro_qhull3.hpp) n_hard is not read: the reference's linearProgram4.
+template <int PS, bool HARD = false>
 __device__ __forceinline__ void w_lp4(const float* planes, int m, int beginPlane, float radius, v3& result,
                       float* proj, int lane
 #ifdef LQRO_LP_PROFILE
                       , int& lp4_iters
 #endif
-                      ) {
+                      , int n_hard = 0) {
   float distance = 0.0f;
   for (int base = beginPlane; base < m; base += 64) {
     const LPPlane pc = ld_plane_if<PS>(planes, base + lane, m);
@@ -313,7 +322,14 @@ __device__ __forceinline__ void w_lp4(const float* planes, int m, int beginPlane
       pi.point = lp_rl3(pc.point, k);
       pi.normal = lp_rl3(pc.normal, k);
       int np = 0;
-      for (int jb = 0; jb < i; jb += 64) {
+      if constexpr (HARD) {
+        for (int p = lane; p < n_hard; p += 64) {
+          const LPPlane ph = ld_plane<PS>(planes, p);
+          st_plane<PS>(proj, p, ph.point, ph.normal);
+        }
+        np = n_hard;
+      }
+      for (int jb = np; jb < i; jb += 64) {
         const int j = jb + lane;
         bool keep = false;
         v3 ppt = V3(0, 0, 0), pnm = V3(0, 0, 0);

@@ -14,7 +14,7 @@ using namespace lqro;
 
 extern "C" {
 
-int lqro_version(void) { return 3; }
+int lqro_version(void) { return 4; }
 
 const char* lqro_status_string(int s) {
   switch (s) {
@@ -170,7 +170,16 @@ int lqro_dynamics_step(const lqro_model* models, int32_t n_models, int32_t n, in
 
 int lqro_calculate_new_v(const float* planes, const int64_t* offsets, int32_t n_agents,
                          const double* vgoal, double vmax_lp, double* newv, int32_t device) {
+  return lqro_calculate_new_v_hard(planes, offsets, nullptr, n_agents, vgoal, vmax_lp, newv, device);
+}
+
+int lqro_calculate_new_v_hard(const float* planes, const int64_t* offsets, const int32_t* n_hard,
+                              int32_t n_agents, const double* vgoal, double vmax_lp, double* newv,
+                              int32_t device) {
   if (!planes || !offsets || !vgoal || !newv || n_agents <= 0) return LQRO_E_ARG;
+  if (n_hard)
+    for (int r = 0; r < n_agents; ++r)
+      if (n_hard[r] < 0) return LQRO_E_ARG;
   HIPCHK(hipSetDevice(device));
   int64_t mmax = 1;
   for (int r = 0; r < n_agents; ++r) {
@@ -190,11 +199,13 @@ int lqro_calculate_new_v(const float* planes, const int64_t* offsets, int32_t n_
   DevPool mem;
   float *d_slots = nullptr, *d_compact = nullptr, *d_proj = nullptr;
   double *d_vg = nullptr, *d_nv = nullptr;
-  int *d_l4 = nullptr, *d_l4c = nullptr;
+  int *d_l4 = nullptr, *d_l4c = nullptr, *d_nh = nullptr;
   if (mem.get(d_slots, 8 * slots) || mem.get(d_compact, 8 * slots) || mem.get(d_proj, 8 * slots) ||
       mem.get(d_vg, 3 * (size_t)n_agents) || mem.get(d_nv, 3 * (size_t)n_agents) ||
-      mem.get(d_l4, 6 * (size_t)n_agents) || mem.get(d_l4c, 2, 0))
+      mem.get(d_l4, 8 * (size_t)n_agents) || mem.get(d_l4c, 2, 0) || (n_hard && mem.get(d_nh, (size_t)n_agents)))
     return LQRO_E_NOMEM;
+  if (n_hard && hipMemcpy(d_nh, n_hard, sizeof(int) * (size_t)n_agents, hipMemcpyHostToDevice) != hipSuccess)
+    return LQRO_E_HIP;
   if (hipMemcpy(d_slots, h.data(), sizeof(float) * 8 * slots, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d_vg, vgoal, sizeof(double) * 3 * n_agents, hipMemcpyHostToDevice) != hipSuccess)
     return LQRO_E_HIP;
@@ -202,6 +213,7 @@ int lqro_calculate_new_v(const float* planes, const int64_t* offsets, int32_t n_
   La.npr = (int)mmax; La.cap = (int)mmax; La.nrows = n_agents; La.row_begin = 0; La.row_stride = 1; La.vmax = vmax_lp;
   La.slots = d_slots; La.compact = d_compact; La.proj = d_proj; La.vgoal = d_vg; La.newv = d_nv; La.prof = nullptr;
   La.lp4_list = d_l4; La.lp4_count = d_l4c; La.lp4_next = d_l4c + 1;
+  La.obs_first = -1; La.nhard_rows = d_nh;   // (the kernel clamps to the row's plane count)
   if (launch_lp(La, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
       hipMemcpy(newv, d_nv, sizeof(double) * 3 * n_agents, hipMemcpyDeviceToHost) != hipSuccess)
     return LQRO_E_HIP;

@@ -130,6 +130,8 @@ struct StepShape {
   int extra_planes = 0;      // fence + user planes a row's LP may get ahead of its pair planes (capacity per row)
   int n_obs = 0;             // obstacle columns behind the npr agent columns of every row (lqro_set_obstacles):
                              //   a row has npr + n_obs slots, whatever the number of rows
+  int hard_obs = 0;          // lqro_set_hard_planes at LQRO_HARD_OBSTACLES with obstacles set: the row's LP takes
+                             //   its obstacle slots ahead of its agent slots
 };
 
 struct StepPlan {
@@ -300,8 +302,10 @@ inline StepPlan plan_step(const StepShape& S, const StepKnobs& K, const StepFeed
   // more than 10,000 points (C5's ~19,000), or builds capped two steps before)
   p.big_inline = K.qhull_inline && !K.qhull_big && (S.hnp > 10000 || retried_prev > 0) ? 1 : 0;
   // (a row with fence or user planes: k_qhull's in-job LP knows the pair
-  // planes only, so the job that closes the row leaves it to the tail)
-  p.row_lp = npr <= S.early_lp_max_npr && S.extra_planes <= 0 ? 1 : 0;
+  // planes only, so the job that closes the row leaves it to the tail; so
+  // does one whose LP takes the obstacle slots first: the in-job LP compacts
+  // in slot order)
+  p.row_lp = npr <= S.early_lp_max_npr && S.extra_planes <= 0 && !S.hard_obs ? 1 : 0;
   p.row_target = p.row_split * S.row_big;
   return p;
 }

@@ -183,7 +183,7 @@ static int ctx_alloc(lqro_ctx* c) {
   BUF(d_hbig, (size_t)c->hull_big_blocks);
   BUF(d_hwide, HULL_CWAVES * hb);
   BUF(d_hbag, HULL_BAGCAP * hb, 0xFF);
-  BUF(d_lp4, 6 * rows, 0);
+  BUF(d_lp4, 8 * rows, 0);
   BUF(d_carry, 6, 0);
   BUF(d_rowpend, 2 * rows, 0);
   c->d_rowclaim = c->d_rowpend + rows;   // (the second half of the same buffer)
@@ -447,6 +447,14 @@ int lqro_set_fence(lqro_ctx* c, const double* lo, const double* hi, double tau) 
   return LQRO_OK;
 }
 
+int lqro_set_hard_planes(lqro_ctx* c, int32_t level) {
+  if (!c || level < LQRO_HARD_NONE || level > LQRO_HARD_OBSTACLES) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;   // the pending half-step's LP was planned with the old level
+  if (int rc = ctx_enter(c, false)) return rc;
+  c->hard_level = level;   // (lp_args and step_shape read it per step; nothing is allocated)
+  return LQRO_OK;
+}
+
 // lqro_set_obstacles / _device.  own: `states` is a host array to copy.
 static int set_obstacles(lqro_ctx* c, const double* states, int M, double oxy, double oz, double resp, bool own) {
   if (!c) return LQRO_E_ARG;
@@ -574,6 +582,10 @@ static LpArgs lp_args(const lqro_ctx* c, int npr, const double* d_vgoal, double*
   La.lp4_list = c->d_lp4; La.lp4_count = c->d_hcount + LQRO_HC_LP4; La.lp4_next = c->d_hcount + LQRO_HC_LP4_NEXT;
   La.fence = c->d_fence; La.nfence = c->nfence;
   La.uplanes = c->d_uplanes; La.ucounts = c->d_ucounts; La.umax = c->uplane_max;
+  // hard planes: at level 3 with obstacles the row's obstacle slots go ahead of its agent slots
+  La.hard = c->hard_level;
+  La.obs_first = c->hard_level >= LQRO_HARD_OBSTACLES && c->nobs > 0 ? c->cfg.n_agents - 1 : -1;
+  La.nbr = c->nbr_k > 0 ? c->d_nbrlist : nullptr;
   return La;
 }
 
@@ -590,6 +602,7 @@ static StepShape step_shape(const lqro_ctx* c, int phase, const double* d_lpnv, 
   S.qhull_lds_doubles = qhull_lds_doubles(); S.lp_lds_max = kLpLdsMax;
   S.early_lp_max_npr = LQRO_EARLY_LP_MAX_NPR; S.row_big = LQRO_ROW_BIG;
   S.extra_planes = c->nfence + c->uplane_max;
+  S.hard_obs = c->hard_level >= LQRO_HARD_OBSTACLES && c->nobs > 0 ? 1 : 0;
   return S;
 }
 

@@ -87,7 +87,10 @@ EXPORTS = (
     "lqro_get_stats_ex", "lqro_get_hull_failures", "lqro_get_hull_builds", "lqro_get_qhmerge_pairs",
     "lqro_set_user_planes", "lqro_set_user_planes_device", "lqro_set_fence",
     "lqro_set_obstacles", "lqro_set_obstacles_device",
+    "lqro_set_hard_planes", "lqro_calculate_new_v_hard",
 )
+# lqro_set_hard_planes' levels: the planes linearProgram4 does not relax
+LQRO_HARD_NONE, LQRO_HARD_FENCE, LQRO_HARD_HEAD, LQRO_HARD_OBSTACLES = 0, 1, 2, 3
 
 NORMALS_PER_AGENT = 22   # LQRO_NORMALS_PER_AGENT: 16 propagate + 6 observation
 
@@ -144,6 +147,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "lqro_set_obstacles"):   # (older libraries in A/B runs lack them)
             L.lqro_set_obstacles.argtypes = [vp, vp, i32, dbl, dbl, dbl]
             L.lqro_set_obstacles_device.argtypes = [vp, vp, i32, dbl, dbl, dbl]
+        if hasattr(L, "lqro_set_hard_planes"):   # (older libraries in A/B runs lack them)
+            L.lqro_set_hard_planes.argtypes = [vp, i32]
+            L.lqro_calculate_new_v_hard.argtypes = [vp, vp, vp, i32, vp, dbl, vp, i32]
         L.lqro_set_carry_normal.argtypes = [vp, vp]
         L.lqro_get_carry_normal.argtypes = [vp, vp]
         _lib = L
@@ -373,6 +379,18 @@ class Context:
                                                float(responsibility)), "lqro_set_obstacles_device")
         self.n_obstacles, self._obs_keep = m, (states if m else None)
 
+    def set_hard_planes(self, level: int):
+        """Which planes linearProgram4 keeps out of its relaxation
+        (lqro_set_hard_planes; RVO2's obstacle lines): LQRO_HARD_NONE (the
+        default), LQRO_HARD_FENCE (the fence planes), LQRO_HARD_HEAD (the user
+        planes too), LQRO_HARD_OBSTACLES (also the obstacle columns' planes,
+        which the LP then takes ahead of the agent planes).  Once the hard
+        planes and the speed sphere are feasible together and the result
+        satisfies them, no later relaxation leaves them; hard planes that are
+        infeasible among themselves guarantee nothing.  The level stays when
+        fence, user planes or obstacles are set or cleared later."""
+        _check(lib().lqro_set_hard_planes(self._h, int(level)), "lqro_set_hard_planes")
+
     def set_gains(self, A, B, L, E, per_agent: bool = False):
         A, B, L, E = (np.ascontiguousarray(v, dtype=np.float64) for v in (A, B, L, E))
         X, U, n = self.cfg.x_dim, self.cfg.u_dim, self.cfg.n_agents
@@ -509,10 +527,12 @@ class Context:
                     step_ms=float(t[3]))
 
 
-def calculate_new_v(plane_lists, vgoals, vmax_lp: float = 100.0, device: int = 0) -> np.ndarray:
+def calculate_new_v(plane_lists, vgoals, vmax_lp: float = 100.0, device: int = 0, n_hard=None) -> np.ndarray:
     """calculateNewV (LQRO:1223-1234) for many agents at once on the GPU.
     plane_lists: sequence of (m_r, 6) float32 arrays (point, normal) in push
-    order; vgoals: (n, 3)."""
+    order; vgoals: (n, 3).  n_hard: per agent, how many of its first planes
+    linearProgram4 does not relax (lqro_calculate_new_v_hard; clamped to the
+    agent's plane count, negative raises); None: none, the reference's LP."""
     n = len(plane_lists)
     offs = np.zeros(n + 1, dtype=np.int64)
     for r, p in enumerate(plane_lists):
@@ -523,6 +543,11 @@ def calculate_new_v(plane_lists, vgoals, vmax_lp: float = 100.0, device: int = 0
             flat[offs[r]:offs[r + 1]] = np.asarray(p, dtype=np.float32).reshape(-1, 6)
     vg = np.ascontiguousarray(vgoals, dtype=np.float64).reshape(n, 3)
     out = np.zeros((n, 3))
+    if n_hard is not None:
+        nh = np.ascontiguousarray(n_hard, dtype=np.int32).reshape(n)
+        _check(lib().lqro_calculate_new_v_hard(_p(flat), _p(offs), _p(nh), n, _p(vg), vmax_lp, _p(out), device),
+               "lqro_calculate_new_v_hard")
+        return out
     _check(lib().lqro_calculate_new_v(_p(flat), _p(offs), n, _p(vg), vmax_lp, _p(out), device),
            "lqro_calculate_new_v")
     return out
@@ -730,6 +755,11 @@ class Simulator:
         """Bodies that are not in qlist as extra columns of every agent's pair
         loop (Context.set_obstacles); None clears."""
         self.ctx.set_obstacles(states, xy_radius, z_radius, responsibility)
+
+    def set_hard_planes(self, level: int):
+        """Which of the fence, user and obstacle planes the LP never relaxes
+        (Context.set_hard_planes)."""
+        self.ctx.set_hard_planes(level)
 
     def step(self):
         x = np.stack([q.x for q in self.qlist])
@@ -948,6 +978,11 @@ class DeviceLoop:
         """This rank's context takes the obstacle set (every rank the same
         arguments); a device tensor is read by every later step."""
         self.ctx.set_obstacles(states, xy_radius, z_radius, responsibility)
+
+    def set_hard_planes(self, level: int):
+        """This rank's context takes the hardness level (every rank the same;
+        Context.set_hard_planes)."""
+        self.ctx.set_hard_planes(level)
 
     def step(self, gather: bool = False):
         """The pair loop for the own rows; newV of the own rows on the device
