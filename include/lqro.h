@@ -277,7 +277,8 @@ int lqro_set_fence(lqro_ctx* ctx, const double lo[3], const double hi[3], double
  *     (z_radius + obs_z_radius), the sum formed first: obstacle radii equal
  *     to the agents' give the agents' set bit for bit, radii (0, 0) give
  *     createFloorSpheres (LQRO:752-767), a point obstacle.  One shape and one
- *     responsibility per context.
+ *     responsibility for all the obstacles of these two calls
+ *     (lqro_set_obstacles_ex below: one of each per obstacle).
  * A row then has n_agents - 1 + M slots: the loop-carried normalVector
  * (LQRO:1385) runs through the obstacle columns like through any pair, the
  * row's LP sees their planes after the agents' (fence and user planes stay
@@ -302,6 +303,44 @@ int lqro_set_obstacles(lqro_ctx* ctx, const double* states /* M*X, host, copied 
 int lqro_set_obstacles_device(lqro_ctx* ctx, const double* d_states /* M*X, read when the step runs */,
                               int32_t n_obstacles, double obs_xy_radius, double obs_z_radius,
                               double responsibility);
+/* A shape and a responsibility per obstacle: a 0.3 m pole, a 5 m balloon
+ * that cooperates at 0.5 and a piloted aircraft that never yields at 1.0 in
+ * one scene.  The two calls above forward here with their three scalars
+ * broadcast, and their results are unchanged bit for bit.
+ *   - Point set.  Obstacle o's column uses createSpheres with (xy_radius +
+ *     xy_radius[o]) and (z_radius + z_radius[o]), the sum formed first, as
+ *     above.  NULL for either array: the agents' radii for every obstacle.
+ *   - Factor.  distance *= responsibility[o] replaces the 0.5 of LQRO:1416 for
+ *     that column.  NULL: 1.0 for every obstacle.
+ *   - Classes.  Distinct shapes are found by comparing the generated point
+ *     sets bit for bit.  A set equal to the agents' uses the agents' tables and
+ *     costs nothing; the others are classes 1..K in order of first
+ *     appearance, each with a point set, a slice bound and a block of k_pair's
+ *     LDS of its own (3 n_points + horizon + 4 doubles).  More than
+ *     LQRO_OBS_SHAPES_MAX classes: LQRO_E_ARG; so is a layout in which the
+ *     class blocks leave no wave of k_pair its LDS region (large horizon x
+ *     n_points), a radius negative or not finite and a responsibility outside
+ *     (0, 1].  With no class of their own the LDS layout, its size and the wave
+ *     count are those the context was created with.
+ *   - Everything else is as above: the column order j = n_agents + o, the
+ *     carried normal, records, statistics, hull failures and merge suspects,
+ *     culling, shards, hard planes, clearing and renumbering, LQRO_E_STATE
+ *     while a lqro_step_device_begin is pending; a failed call leaves the
+ *     context as it was.
+ *   - Culling.  lqro_set_neighbors ranks candidates by centre distance, the
+ *     obstacles among them: with culling on, a large obstacle can be dropped
+ *     from a row's list while its surface is near.  Give max_neighbors room for
+ *     the obstacles in range, or leave culling off with large shapes.
+ * The three arrays are host arrays of n_obstacles doubles, copied by both
+ * calls; only the states of the _device call stay the caller's. */
+#define LQRO_OBS_SHAPES_MAX 8
+int lqro_set_obstacles_ex(lqro_ctx* ctx, const double* states /* M*X, host, copied */, int32_t n_obstacles,
+                          const double* xy_radius /* M, host; NULL: the agents' */,
+                          const double* z_radius /* M, host; NULL: the agents' */,
+                          const double* responsibility /* M, host; NULL: all 1.0 */);
+int lqro_set_obstacles_ex_device(lqro_ctx* ctx, const double* d_states /* M*X, read when the step runs */,
+                                 int32_t n_obstacles, const double* xy_radius, const double* z_radius,
+                                 const double* responsibility);
 
 /* ---- hard planes: constraints linearProgram4 does not relax ------------
  * The fence, user and obstacle planes above are as soft as the pair planes:

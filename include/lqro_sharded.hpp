@@ -183,6 +183,21 @@ class ShardedSimulator {
                              responsibility),
           "lqro_set_obstacles");
   }
+  // ... with a shape and a responsibility per obstacle (lqro_set_obstacles_ex;
+  // an empty vector: the default)
+  void setObstacles(const std::vector<std::array<double, kX>>& states, const std::vector<double>& xy_radius,
+                    const std::vector<double>& z_radius, const std::vector<double>& responsibility) {
+    if (!ctx_) return;
+    std::vector<double> flat;
+    for (const auto& st : states) flat.insert(flat.end(), st.begin(), st.end());
+    for (const std::vector<double>* v : {&xy_radius, &z_radius, &responsibility})
+      if (!v->empty() && v->size() != states.size()) check(LQRO_E_ARG, "setObstacles: one value per obstacle");
+    check(lqro_set_obstacles_ex(ctx_, flat.empty() ? nullptr : flat.data(), (int32_t)states.size(),
+                                xy_radius.empty() ? nullptr : xy_radius.data(),
+                                z_radius.empty() ? nullptr : z_radius.data(),
+                                responsibility.empty() ? nullptr : responsibility.data()),
+          "lqro_set_obstacles_ex");
+  }
 
   // Simulator::setHardPlanes for this rank's context: every rank passes the
   // same level (lqro_set_hard_planes)

@@ -105,9 +105,11 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   const double* d_obs;            // nobs x X: the caller's, or d_obsown
   double* d_obsown;               // lqro_set_obstacles's copy
   double* d_cols;                 // (n_agents + nobs) x X
-  double obs_resp;                // the obstacle columns' factor for the 0.5 of LQRO:1416
-  int obs_shape;                  // 1: a point set of their own (d_So, d_Ro; pa.orad*, pa.oumax), 0: the agents'
-  double *d_So, *d_Ro;            // NP x 3; n_agents x H (the row of agent 0 with shared gains)
+  int n_ocls;                     // shape classes that are not the agents' (<= LQRO_OBS_SHAPES_MAX)
+  double* d_oresp;                // nobs: each column's factor for the 0.5 of LQRO:1416
+  int* d_ocls;                    // nobs: 0 the agents' shape, c >= 1 class c (n_ocls > 0 only)
+  double *d_So, *d_Ro;            // n_ocls x (NP x 3), then n_ocls x 4 (semi-axes, max |u_p|: pa.osc);
+                                  // n_ocls x n_agents x H (the row of agent 0 with shared gains)
   int lds_attr;                   // the dynamic LDS size the k_pair instantiations are set to
   lqro::PairArgs pa;
   lqro::DevPool mem;              // owns every d_* buffer above that is not the caller's

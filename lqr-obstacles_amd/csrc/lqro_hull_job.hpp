@@ -113,40 +113,46 @@ struct HullArgs {
   // own LDS (rows of at most LQRO_EARLY_LP_MAX_NPR pairs); 0: such rows are
   // left to the tail
   int row_lp;
-  // obstacle columns (lqro_set_obstacles; So null: none): x holds the agents'
-  // states, then the obstacles'; a row's slots jj >= obs_jj (= agents - 1) are
-  // the obstacles', with their own point set So (== S for the agents' shape)
-  // and obs_resp for the 0.5 of LQRO:1416
+  // obstacle columns (lqro_set_obstacles[_ex]; oresp null: none): x holds the
+  // agents' states, then the obstacles'; a row's slots jj >= obs_jj (= agents
+  // - 1) are the obstacles'.  Obstacle o takes oresp[o] for the 0.5 of
+  // LQRO:1416 and the point set of its class ocls[o] (null: every class 0):
+  // 0 the agents' S, c >= 1 So + (c - 1) * NP * 3
   const double* So;
+  const int* ocls;
+  const double* oresp;
   int obs_jj;
-  double obs_resp;
 };
 
 // Which of a row's slots are obstacle columns, for the kernels that finish a
 // half-plane outside the hull kernels (k_stale, k_stale_rows): slot jj >= jj
-// (through nbr_list with culling on) takes resp.  on null: no obstacles.
+// (through nbr_list with culling on) takes resp[jj - jj0].  resp null: no
+// obstacles.
 struct ObsSlots {
-  const void* on;
+  const double* resp;
   const int* nbr_list;
   int jj;
-  double resp;
 };
 
 // the factor of LQRO:1416 for a slot's half-plane: 0.5 between agents, the
-// context's responsibility for an obstacle column (LQRO:1434: 1.0)
-__device__ __forceinline__ double slot_factor(const int* nbr_list, int npr, long slot, const void* have_obs,
-                                              int obs_jj, double obs_resp) {
-  if (!have_obs) return 0.5;
+// obstacle's own responsibility for an obstacle column (LQRO:1434: 1.0)
+__device__ __forceinline__ double slot_factor(const int* nbr_list, int npr, long slot, const double* oresp,
+                                              int obs_jj) {
+  if (!oresp) return 0.5;
   const int jj = nbr_list ? nbr_list[slot] : (int)(slot % npr);
-  return jj >= obs_jj ? obs_resp : 0.5;
+  return jj >= obs_jj ? oresp[jj - obs_jj] : 0.5;
 }
 __device__ __forceinline__ double hull_factor(const HullArgs& A, int slot) {
-  return slot_factor(A.nbr_list, A.npr, slot, A.So, A.obs_jj, A.obs_resp);
+  return slot_factor(A.nbr_list, A.npr, slot, A.oresp, A.obs_jj);
 }
 // the point set of the column whose state is xj (x's rows past the agents'
-// are the obstacles')
+// are the obstacles'): its class's
 __device__ __forceinline__ const double* hull_col_sphere(const HullArgs& A, const double* xj) {
-  return (A.So && xj >= A.x + ((size_t)A.obs_jj + 1) * A.X) ? A.So : A.S;
+  if (!A.ocls) return A.S;
+  const double* x0 = A.x + ((size_t)A.obs_jj + 1) * A.X;
+  if (xj < x0) return A.S;
+  const int cl = A.ocls[(xj - x0) / A.X];
+  return cl > 0 ? A.So + (size_t)(cl - 1) * A.NP * 3 : A.S;
 }
 
 // (LQRO_ROW_BIG, lqro_device.hpp: the row counter's protocol; the early LP

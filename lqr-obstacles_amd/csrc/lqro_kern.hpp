@@ -75,9 +75,10 @@ struct ObsSlots;   // (lqro_hull_job.hpp)
 void launch_tables(hipStream_t s, int n_gains, int X, int U, int H, const double* A, const double* B, const double* L,
                    const double* E, int per_agent, double* T, double* NCF, double* R, double* TF, double rad0,
                    double rad1, double rad2, double umax, int* err);
-// k_obs_rtab: the obstacle columns' slice bound (PairArgs::Ro) from the tables' T
-void launch_obs_rtab(hipStream_t s, int n_gains, int H, const double* T, double* Ro, double rad0, double rad1,
-                     double rad2, double umax);
+// k_obs_rtab: the obstacle classes' slice bounds (PairArgs::Ro: class, agent of n_agents, H) from the tables' T
+// and each class's semi-axes and max |u_p| (osc), one launch over (class, agent, k)
+void launch_obs_rtab(hipStream_t s, int n_cls, int n_gains, int n_agents, int H, const double* T, const double* osc,
+                     double* Ro);
 // k_cols: the step's columns, the agents' states then the obstacles'
 void launch_cols(hipStream_t s, const double* x, size_t nx, const double* obs, size_t nobs, double* cols);
 constexpr size_t kLpLdsMax = 160 * 1024;   // one CU's LDS: the longest plane list k_lp_lds holds

@@ -287,21 +287,25 @@ __global__ void __launch_bounds__(256) k_fence(FenceArgs F) {
     }
   }
 }
-// The obstacle columns' slice bound (lqro_set_obstacles with a shape of its
-// own): k_tables' R with the obstacles' semi-axes, from the T it left.
-__global__ void __launch_bounds__(256) k_obs_rtab(int n, const double* __restrict__ T, double* __restrict__ Ro,
-                                                  double rad0, double rad1, double rad2, double umax) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;   // (agent, k)
+// The obstacle classes' slice bounds (lqro_set_obstacles[_ex] with shapes of
+// their own): k_tables' R with each class's semi-axes and max |u_p| (osc, 4
+// a class), from the T it left.  Ro is (class, agent of n_agents, k); the
+// first n_gains agents of a class are written.
+__global__ void __launch_bounds__(256) k_obs_rtab(int n, int per_cls, int cls_pitch, const double* __restrict__ T,
+                                                  const double* __restrict__ osc, double* __restrict__ Ro) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;   // (class, agent, k)
   if (q >= n) return;
-  const double* inv = T + (size_t)q * 9;
-  const double rad[3] = {rad0, rad1, rad2};
+  const int c = q / per_cls, ak = q - c * per_cls;
+  const double* inv = T + (size_t)ak * 9;
+  const double rad[3] = {osc[4 * c], osc[4 * c + 1], osc[4 * c + 2]};
+  const double umax = osc[4 * c + 3];
   double fr = 0.0;
   for (int rr = 0; rr < 3; ++rr)
     for (int cc = 0; cc < 3; ++cc) {
       const double tv = inv[rr * 3 + cc];
       fr += (tv * rad[cc]) * (tv * rad[cc]);
     }
-  Ro[q] = sqrt(fr) * umax * (1.0 + 1e-12);
+  Ro[(size_t)c * cls_pitch + ak] = sqrt(fr) * umax * (1.0 + 1e-12);
 }
 
 // The step's columns in one array: the agents' states, then the obstacles'
@@ -316,10 +320,11 @@ __global__ void __launch_bounds__(256) k_cols(const double* __restrict__ x, size
 
 namespace lqro {
 
-void launch_obs_rtab(hipStream_t s, int n_gains, int H, const double* T, double* Ro, double rad0, double rad1,
-                     double rad2, double umax) {
-  const int n = n_gains * H;
-  hipLaunchKernelGGL(k_obs_rtab, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, T, Ro, rad0, rad1, rad2, umax);
+void launch_obs_rtab(hipStream_t s, int n_cls, int n_gains, int n_agents, int H, const double* T, const double* osc,
+                     double* Ro) {
+  const int n = n_cls * n_gains * H;
+  hipLaunchKernelGGL(k_obs_rtab, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, n_gains * H, n_agents * H, T, osc,
+                     Ro);
 }
 
 void launch_cols(hipStream_t s, const double* x, size_t nx, const double* obs, size_t nobs, double* cols) {

@@ -14,7 +14,7 @@ using namespace lqro;
 
 extern "C" {
 
-int lqro_version(void) { return 4; }
+int lqro_version(void) { return 5; }
 
 const char* lqro_status_string(int s) {
   switch (s) {

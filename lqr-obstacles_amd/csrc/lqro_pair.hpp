@@ -84,18 +84,23 @@ struct PairArgs {
   int* rowpend;                       // early LP: per row open work (LQRO_ROW_BIG), null: off
   // obstacle columns (lqro_set_obstacles): x then holds the agents' states
   // followed by the obstacles', and a row's slots jj >= obs_jj (= agents - 1)
-  // are the obstacles' (INT_MAX: none).  They take obs_resp for the 0.5 of
-  // LQRO:1416 and their own point set: So (NP x 3), its semi-axes and max |u_p|,
-  // Ro (per agent H, as R).  A shape equal to the agents' shares S, R and
-  // their LDS (lds_So == lds_S, lds_Ro == lds_R)
+  // are the obstacles' (INT_MAX: none).  Obstacle o takes oresp[o] for the
+  // 0.5 of LQRO:1416 and the point set of its shape class ocls[o]: 0 the
+  // agents' (S, R and their LDS), c >= 1 one of the n_cls classes with a
+  // shape of their own: So (class c - 1: NP x 3), osc (its three semi-axes and
+  // max |u_p|), Ro (class, agent, H, as R: n_gain = n_agents rows a class,
+  // agent 0's with shared gains), staged into the class's LDS block
+  // (lqro_plan.hpp pair_layout: S_c SoA, Ro_c, the four scalars)
   int obs_jj;
-  double obs_resp;
-  double orad0, orad1, orad2, oumax;
+  int n_cls, n_gain;
+  const int* ocls;
+  const double* oresp;
   const double* So;
+  const double* osc;
   const double* Ro;
   // LDS layout, in doubles
   int XP, lds_T, lds_N, lds_S, lds_R, lds_TF, lds_H, lds_wave, wave_doubles;
-  int lds_So, lds_Ro;                 // behind lds_H when the obstacles have a shape of their own
+  int lds_cls, cls_doubles;           // behind lds_H: one block per class with a shape of its own
 };
 
 struct BlockTabs {
@@ -491,8 +496,21 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
   double* sS = lds + P.lds_S;
   double* sR = lds + P.lds_R;
   double* sTF = lds + P.lds_TF;
-  double* sSo = lds + P.lds_So;   // (== sS, sR unless the obstacles have a shape of their own)
-  double* sRo = lds + P.lds_Ro;
+  // class c's block: S_c (SoA), Ro_c, the semi-axes and max |u_p|; the
+  // slice bound of agent `ag` (-1: not staged, the hot per-agent launch reads
+  // it from global memory)
+  auto stage_classes = [&](const long ag) {
+    for (int c = 0; c < P.n_cls; ++c) {
+      double* blk = lds + P.lds_cls + c * P.cls_doubles;
+      const double* Sc = P.So + (size_t)c * NP * 3;
+      for (int q = threadIdx.x; q < NP * 3; q += blockDim.x) blk[(q % 3) * NP + q / 3] = Sc[q];
+      if (ag >= 0) {
+        const double* Rc = P.Ro + ((size_t)c * P.n_gain + ag) * H;
+        for (int q = threadIdx.x; q < H; q += blockDim.x) blk[3 * NP + q] = Rc[q];
+      }
+      if (threadIdx.x < 4) blk[3 * NP + H + threadIdx.x] = P.osc[4 * c + threadIdx.x];
+    }
+  };
   unsigned long long* sH = reinterpret_cast<unsigned long long*>(lds + P.lds_H);
   BlockTabs B;
   B.T = sT; B.N = sN; B.S = sS; B.R = sR; B.TF = sTF; B.shash = sH; B.pitch = XP;
@@ -543,21 +561,27 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
       return;
     }
     const int j = jq < i ? jq : jq + 1;
-    // an obstacle column: its own sphere and slice bound (in the same LDS
-    // tables when the shape is the agents')
+    // an obstacle column: its class's sphere, slice bound, semi-axes and max
+    // |u_p| from the class's LDS block (class 0, the agents' shape: the
+    // agents' tables); one base pointer, the scalars wave-uniform
     const bool obs = jq >= P.obs_jj;
     BlockTabs Bj = B;
-    if (obs) {
-      Bj.S = sSo;
-      if constexpr (HOT == kHotPerAgent) Bj.R = P.Ro + (size_t)i * H;
-      else Bj.R = sRo;
+    double cr0 = P.rad0, cr1 = P.rad1, cr2 = P.rad2, cum = P.umax;
+    if (obs && P.n_cls > 0) {
+      const int cl = __builtin_amdgcn_readfirstlane(P.ocls[jq - P.obs_jj]);
+      if (cl > 0) {
+        const double* blk = lds + P.lds_cls + (cl - 1) * P.cls_doubles;
+        Bj.S = blk;
+        if constexpr (HOT == kHotPerAgent) Bj.R = P.Ro + ((size_t)(cl - 1) * P.n_gain + i) * H;
+        else Bj.R = blk + 3 * NP;
+        const double* sc = blk + 3 * NP + H;
+        cr0 = uniform(sc[0]); cr1 = uniform(sc[1]); cr2 = uniform(sc[2]); cum = uniform(sc[3]);
+      }
     }
 #ifdef LQRO_PAIR_PROFILE
-    SliceSupport sp{P, Bj, W, ln, pc, obs ? P.orad0 : P.rad0, obs ? P.orad1 : P.rad1, obs ? P.orad2 : P.rad2,
-                    obs ? P.oumax : P.umax};
+    SliceSupport sp{P, Bj, W, ln, pc, cr0, cr1, cr2, cum};
 #else
-    SliceSupport sp{P, Bj, W, ln, obs ? P.orad0 : P.rad0, obs ? P.orad1 : P.rad1, obs ? P.orad2 : P.rad2,
-                    obs ? P.oumax : P.umax};
+    SliceSupport sp{P, Bj, W, ln, cr0, cr1, cr2, cum};
 #endif
     const double* xj = P.x + (size_t)j * X;
     double d[X];
@@ -707,7 +731,7 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
       flags = LQRO_REC_PLANE | (inside ? LQRO_REC_INSIDE : 0) | (go.backup ? LQRO_REC_BACKUP : 0);
       dist = distance;
       if (!inside) {
-        distance *= obs ? P.obs_resp : 0.5;                     // :1416 (an obstacle: LQRO:1434)
+        distance *= obs ? P.oresp[jq - P.obs_jj] : 0.5;         // :1416 (an obstacle: LQRO:1434, its own share)
         const double mult = -1.0;                               // :1215
         pl[0] = (float)(xi[3] + mult * distance * nrm[0]);      // :1217
         pl[1] = (float)(xi[4] + mult * distance * nrm[1]);
@@ -800,12 +824,9 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
         sR[q] = P.R[q];
         sTF[q] = P.TF[q];
       }
-      if (P.lds_Ro != P.lds_R)
-        for (int q = threadIdx.x; q < H; q += blockDim.x) sRo[q] = P.Ro[q];
     }
     for (int q = threadIdx.x; q < NP * 3; q += blockDim.x) sS[(q % 3) * NP + q / 3] = P.S[q];
-    if (P.lds_So != P.lds_S)
-      for (int q = threadIdx.x; q < NP * 3; q += blockDim.x) sSo[(q % 3) * NP + q / 3] = P.So[q];
+    stage_classes(HOT == kHotShared ? 0 : -1);
     for (int q = threadIdx.x; q < H; q += blockDim.x) sH[q] = P.shash[q];
     __syncthreads();
     const int nhot = min(*P.hot_count, P.hot_cap);
@@ -875,11 +896,7 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
         sTF[q] = TFi[q];
         sH[q] = P.shash[q];
       }
-      if (P.lds_So != P.lds_S) {   // the obstacle columns' sphere and slice bound
-        const double* Roi = P.Ro + ag * H;
-        for (int q = threadIdx.x; q < NP * 3; q += blockDim.x) sSo[(q % 3) * NP + q / 3] = P.So[q];
-        for (int q = threadIdx.x; q < H; q += blockDim.x) sRo[q] = Roi[q];
-      }
+      stage_classes(ag);   // the obstacle classes' spheres and slice bounds
       staged = ag;
       __syncthreads();
     }

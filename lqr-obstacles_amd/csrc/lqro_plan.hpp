@@ -150,6 +150,46 @@ struct StepPlan {
   int big_inline, row_lp, row_target;
 };
 
+// LDS layout of k_pair, in doubles: the block tables (T, N, S, R, TF, the
+// slice hashes), one block per obstacle shape class that is not the agents'
+// (lqro_set_obstacles_ex: S_c 3 NP SoA, Ro_c H, the three semi-axes and max
+// |u_p|), then one region per wave.  n_cls = 0 is the layout a context is
+// created with.
+struct PairLayout {
+  int XP, PW;
+  int lds_T, lds_N, lds_S, lds_R, lds_TF, lds_H;
+  int lds_cls, cls_doubles;   // class c >= 1 at lds_cls + (c - 1) * cls_doubles
+  int lds_wave, wave_doubles, waves;
+  int lds_bytes;
+};
+constexpr int kPairLdsBudget = 160 * 1024 / 8;
+
+// False when no wave keeps a region.  max_waves: LQRO_PAIR_LB / 64.
+inline bool pair_layout(int H, int NP, int X, int n_cls, PairLayout& L, int max_waves = 16) {
+  const int XP = X + 1;
+  int off = 0;
+  L.XP = XP;
+  L.PW = (NP + 63) / 64;
+  L.lds_T = off; off += H * 9;
+  L.lds_N = off; off += H * 3 * XP;
+  L.lds_S = off; off += 3 * NP;
+  L.lds_R = off; off += H;
+  L.lds_TF = off; off += H;
+  L.lds_H = off; off += H;
+  L.lds_cls = off;
+  L.cls_doubles = 3 * NP + H + 4;
+  off += n_cls * L.cls_doubles;
+  L.lds_wave = off;
+  // tr 3H, sc H, mask H*PW (u64), cls/cnt/mixed 3H ints (mixed padded to
+  // even), GJK simplex 18, statistics 5
+  L.wave_doubles = 4 * H + H * L.PW + H + (H + (H & 1)) / 2 + 18 + 5;
+  int waves = off <= kPairLdsBudget ? (kPairLdsBudget - off) / L.wave_doubles : 0;
+  if (waves > max_waves) waves = max_waves;
+  L.waves = waves;
+  L.lds_bytes = (off + (waves > 0 ? waves : 0) * L.wave_doubles) * 8;
+  return waves >= 1;
+}
+
 // The side's width in Qhull order from the work measured two steps before:
 // with k side CUs the builds end no sooner than max(b_max, 1.15 w_build / k)
 // (LPT packing of chains, 15 % margin) and the sweep's rows no sooner than

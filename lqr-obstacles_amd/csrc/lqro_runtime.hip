@@ -200,38 +200,20 @@ static int ctx_alloc(lqro_ctx* c) {
   return LQRO_OK;
 }
 
-// LDS layout of k_pair (in doubles): block tables, then one region per wave.
-// obs_shape: the obstacle columns' own sphere and slice bound behind the
-// agents' tables (lqro_set_obstacles); without, the layout a context is
-// created with.  False when no wave's region fits.
-static bool pair_layout(const lqro_config& g, bool obs_shape, PairArgs& P, int& lds_bytes) {
-  const int H = g.horizon, NP = g.n_points, X = g.x_dim, XP = X + 1;
-  int off = 0;
-  P.XP = XP;
-  P.PW = (NP + 63) / 64;
-  P.lds_T = off; off += H * 9;
-  P.lds_N = off; off += H * 3 * XP;
-  P.lds_S = off; off += 3 * NP;
-  P.lds_R = off; off += H;
-  P.lds_TF = off; off += H;
-  P.lds_H = off; off += H;
-  P.lds_So = P.lds_S; P.lds_Ro = P.lds_R;
-  if (obs_shape) {
-    P.lds_So = off; off += 3 * NP;
-    P.lds_Ro = off; off += H;
-  }
-  P.lds_wave = off;
-  // tr 3H, sc H, mask H*PW (u64), cls/cnt/mixed 3H ints (mixed padded to
-  // even), GJK simplex 18, statistics 5
-  P.wave_doubles = 4 * H + H * P.PW + H + (H + (H & 1)) / 2 + 18 + 5;
-  const int budget = 160 * 1024 / 8;
-  int waves = (budget - off) / P.wave_doubles;
-  if (waves > LQRO_PAIR_LB / 64) waves = LQRO_PAIR_LB / 64;
-  if (waves < 1) return false;
-  P.waves = waves;
-  P.max_waves = waves;
-  off += waves * P.wave_doubles;
-  lds_bytes = off * 8;
+// k_pair's LDS layout (lqro_plan.hpp pair_layout) into its arguments.
+// n_cls: the obstacle shape classes that are not the agents'
+// (lqro_set_obstacles[_ex]); 0: the layout a context is created with.  False
+// when no wave's region fits.
+static bool pair_layout(const lqro_config& g, int n_cls, PairArgs& P, int& lds_bytes) {
+  PairLayout L{};
+  if (!pair_layout(g.horizon, g.n_points, g.x_dim, n_cls, L, LQRO_PAIR_LB / 64)) return false;
+  P.XP = L.XP; P.PW = L.PW;
+  P.lds_T = L.lds_T; P.lds_N = L.lds_N; P.lds_S = L.lds_S; P.lds_R = L.lds_R; P.lds_TF = L.lds_TF; P.lds_H = L.lds_H;
+  P.lds_cls = L.lds_cls; P.cls_doubles = L.cls_doubles; P.n_cls = n_cls;
+  P.lds_wave = L.lds_wave; P.wave_doubles = L.wave_doubles;
+  P.waves = L.waves;
+  P.max_waves = L.waves;
+  lds_bytes = L.lds_bytes;
   return true;
 }
 
@@ -284,7 +266,7 @@ int lqro_create(const lqro_config* cfg, lqro_ctx** out) {
   PairArgs& P = c->pa;
   P.obs_jj = INT_MAX;   // (no obstacle columns)
   int lds_bytes = 0;
-  if (!pair_layout(g, false, P, lds_bytes)) {
+  if (!pair_layout(g, 0, P, lds_bytes)) {
     fprintf(stderr, "liblqro: horizon %d x %d points does not fit in LDS\n", H, NP);
     delete c;
     return LQRO_E_ARG;
@@ -455,48 +437,80 @@ int lqro_set_hard_planes(lqro_ctx* c, int32_t level) {
   return LQRO_OK;
 }
 
-// lqro_set_obstacles / _device.  own: `states` is a host array to copy.
-static int set_obstacles(lqro_ctx* c, const double* states, int M, double oxy, double oz, double resp, bool own) {
+// lqro_set_obstacles[_ex] / _device.  own: `states` is a host array to copy.
+// oxy, oz, resp: one value per obstacle (host).
+static int set_obstacles(lqro_ctx* c, const double* states, int M, const double* oxy, const double* oz,
+                         const double* resp, bool own) {
   if (!c) return LQRO_E_ARG;
   if (c->pending) return LQRO_E_STATE;   // the pending half-step's tail still reads the slots
   const lqro_config& g = c->cfg;
   if (M <= 0 || !states) M = 0;
   if (M > 0) {
-    if (!(oxy >= 0) || !(oz >= 0) || !std::isfinite(oxy) || !std::isfinite(oz) || !(resp > 0 && resp <= 1))
-      return LQRO_E_ARG;
+    for (int o = 0; o < M; ++o)
+      if (!(oxy[o] >= 0) || !(oz[o] >= 0) || !std::isfinite(oxy[o]) || !std::isfinite(oz[o]) ||
+          !(resp[o] > 0 && resp[o] <= 1))
+        return LQRO_E_ARG;
     if ((long long)c->nrows * ((long long)g.n_agents - 1 + M) > (long long)INT_MAX) return LQRO_E_ARG;   // (slots are ints)
   }
   if (int rc = ctx_enter(c, false)) return rc;
   const size_t N = g.n_agents, X = g.x_dim, H = g.horizon, NP = g.n_points;
-  // the obstacle columns' sphere: createSpheres over the summed radii; the
-  // agents' tables serve when it is theirs bit for bit
-  std::vector<double> So;
-  bool shape = false;
+  // the obstacle columns' spheres: createSpheres over the summed radii, the
+  // distinct ones found bit for bit; the agents' tables serve a set that is
+  // theirs (class 0), the others are classes 1..K in order of first appearance
+  std::vector<double> So;    // K x (NP x 3)
+  std::vector<double> osc;   // K x (semi-axes, max |u_p|)
+  std::vector<int> ocls((size_t)M, 0);
+  int K = 0;
   if (M > 0) {
-    std::vector<double> S(3 * NP);
-    So.resize(3 * NP);
+    std::vector<double> S(3 * NP), So_o(3 * NP);
     lqro_sphere((int)NP, g.xy_radius, g.z_radius, S.data());
-    sphere_axes((int)NP, g.xy_radius + oxy, g.z_radius + oz, So.data());
-    shape = memcmp(S.data(), So.data(), sizeof(double) * So.size()) != 0;
+    for (int o = 0; o < M; ++o) {
+      int cl = -1;
+      for (int p = 0; p < o && cl < 0; ++p)   // (the same radii: the same set)
+        if (memcmp(&oxy[p], &oxy[o], sizeof(double)) == 0 && memcmp(&oz[p], &oz[o], sizeof(double)) == 0) cl = ocls[p];
+      if (cl < 0) {
+        sphere_axes((int)NP, g.xy_radius + oxy[o], g.z_radius + oz[o], So_o.data());
+        if (memcmp(S.data(), So_o.data(), sizeof(double) * 3 * NP) == 0) cl = 0;
+        for (int k = 0; k < K && cl < 0; ++k)
+          if (memcmp(So.data() + (size_t)k * 3 * NP, So_o.data(), sizeof(double) * 3 * NP) == 0) cl = k + 1;
+        if (cl < 0) {
+          if (K == LQRO_OBS_SHAPES_MAX) return LQRO_E_ARG;
+          So.insert(So.end(), So_o.begin(), So_o.end());
+          const double rad[3] = {g.xy_radius + oxy[o], g.xy_radius + oxy[o], g.z_radius + oz[o]};
+          osc.insert(osc.end(), rad, rad + 3);
+          osc.push_back(sphere_umax(So_o.data(), (int)NP, rad));
+          cl = ++K;
+        }
+      }
+      ocls[o] = cl;
+    }
   }
   PairArgs pa = c->pa;
   int lds_bytes = 0;
-  if (!pair_layout(g, shape, pa, lds_bytes)) return LQRO_E_ARG;   // (H x NP leaves no room for a second sphere)
+  if (!pair_layout(g, K, pa, lds_bytes)) return LQRO_E_ARG;   // (H x NP leaves no wave a region beside K more spheres)
   // every new buffer first: a failed call leaves the context as it was
   const int npr = (int)N - 1 + M;
-  double *cols = nullptr, *copy = nullptr, *dSo = nullptr, *dRo = nullptr;
+  double *cols = nullptr, *copy = nullptr, *dSo = nullptr, *dRo = nullptr, *dresp = nullptr;
+  int* dcls = nullptr;
   SlotBufs sb{};
   int rc = LQRO_OK;
-  if (M > 0 && c->mem.get(cols, (N + M) * X)) rc = LQRO_E_NOMEM;
+  if (M > 0 && (c->mem.get(cols, (N + M) * X) || c->mem.get(dresp, (size_t)M))) rc = LQRO_E_NOMEM;
   if (!rc && M > 0 && own && c->mem.get(copy, (size_t)M * X)) rc = LQRO_E_NOMEM;
-  if (!rc && shape && (c->mem.get(dSo, 3 * NP) || c->mem.get(dRo, N * H))) rc = LQRO_E_NOMEM;
+  if (!rc && K > 0 && (c->mem.get(dSo, (size_t)K * (3 * NP + 4)) || c->mem.get(dRo, (size_t)K * N * H) ||
+                       c->mem.get(dcls, (size_t)M)))
+    rc = LQRO_E_NOMEM;
   if (!rc && npr != c->npr) rc = slots_alloc(c, npr, sb);
   if (!rc && copy && hipMemcpy(copy, states, sizeof(double) * M * X, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
-  if (!rc && shape && hipMemcpy(dSo, So.data(), sizeof(double) * So.size(), hipMemcpyHostToDevice) != hipSuccess)
+  if (!rc && M > 0 && hipMemcpy(dresp, resp, sizeof(double) * M, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  if (!rc && K > 0 &&
+      (hipMemcpy(dSo, So.data(), sizeof(double) * So.size(), hipMemcpyHostToDevice) != hipSuccess ||
+       hipMemcpy(dSo + So.size(), osc.data(), sizeof(double) * osc.size(), hipMemcpyHostToDevice) != hipSuccess ||
+       hipMemcpy(dcls, ocls.data(), sizeof(int) * M, hipMemcpyHostToDevice) != hipSuccess))
     rc = LQRO_E_HIP;
   if (!rc && !pair_set_lds(lds_bytes)) rc = LQRO_E_HIP;
   if (rc) {
     c->mem.release(cols); c->mem.release(copy); c->mem.release(dSo); c->mem.release(dRo);
+    c->mem.release(dresp); c->mem.release(dcls);
     slots_release(c, sb);
     (void)pair_set_lds(c->lds_bytes);
     return rc;
@@ -513,36 +527,58 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, double oxy, d
     c->nstep = 0;
   }
   c->mem.release(c->d_cols); c->mem.release(c->d_obsown); c->mem.release(c->d_So); c->mem.release(c->d_Ro);
-  c->d_cols = cols; c->d_obsown = copy; c->d_So = dSo; c->d_Ro = dRo;
+  c->mem.release(c->d_oresp); c->mem.release(c->d_ocls);
+  c->d_cols = cols; c->d_obsown = copy; c->d_So = dSo; c->d_Ro = dRo; c->d_oresp = dresp; c->d_ocls = dcls;
   c->d_obs = M > 0 ? (own ? copy : states) : nullptr;
   c->nobs = M;
-  c->obs_resp = M > 0 ? resp : 0.0;
-  c->obs_shape = shape ? 1 : 0;
-  pa.orad0 = pa.orad1 = shape ? g.xy_radius + oxy : pa.rad0;
-  pa.orad2 = shape ? g.z_radius + oz : pa.rad2;
-  pa.oumax = pa.umax;
-  if (shape) {
-    const double rad[3] = {pa.orad0, pa.orad1, pa.orad2};
-    pa.oumax = sphere_umax(So.data(), (int)NP, rad);
-  }
+  c->n_ocls = K;
+  pa.n_gain = (int)N;
+  pa.ocls = dcls; pa.oresp = dresp;
+  pa.So = dSo; pa.osc = K > 0 ? dSo + So.size() : nullptr; pa.Ro = dRo;
   c->pa = pa;
   c->lds_bytes = lds_bytes;
-  if (shape && c->have_gains) {   // (else lqro_set_gains builds it with its tables)
-    LAUNCH(launch_obs_rtab(c->stream, c->per_agent ? (int)N : 1, (int)H, c->d_T, c->d_Ro, pa.orad0, pa.orad1, pa.orad2,
-                           pa.oumax));
+  if (K > 0 && c->have_gains) {   // (else lqro_set_gains builds it with its tables)
+    LAUNCH(launch_obs_rtab(c->stream, K, c->per_agent ? (int)N : 1, (int)N, (int)H, c->d_T, pa.osc, c->d_Ro));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return LQRO_OK;
 }
 
+// the _ex calls' NULL arrays: the agents' radii, responsibility 1.0
+static int set_obstacles_arrays(lqro_ctx* c, const double* states, int M, const double* oxy, const double* oz,
+                                const double* resp, bool own) {
+  if (!c) return LQRO_E_ARG;
+  const size_t m = M > 0 && states ? (size_t)M : 0;
+  std::vector<double> dxy, dz, dr;
+  if (!oxy) { dxy.assign(m, c->cfg.xy_radius); oxy = dxy.data(); }
+  if (!oz) { dz.assign(m, c->cfg.z_radius); oz = dz.data(); }
+  if (!resp) { dr.assign(m, 1.0); resp = dr.data(); }
+  return set_obstacles(c, states, (int)m, oxy, oz, resp, own);
+}
+
+int lqro_set_obstacles_ex(lqro_ctx* c, const double* states, int32_t n_obstacles, const double* xy_radius,
+                          const double* z_radius, const double* responsibility) {
+  return set_obstacles_arrays(c, states, n_obstacles, xy_radius, z_radius, responsibility, true);
+}
+
+int lqro_set_obstacles_ex_device(lqro_ctx* c, const double* d_states, int32_t n_obstacles, const double* xy_radius,
+                                 const double* z_radius, const double* responsibility) {
+  return set_obstacles_arrays(c, d_states, n_obstacles, xy_radius, z_radius, responsibility, false);
+}
+
+// the one-shape calls: their three scalars broadcast
 int lqro_set_obstacles(lqro_ctx* c, const double* states, int32_t n_obstacles, double obs_xy_radius,
                        double obs_z_radius, double responsibility) {
-  return set_obstacles(c, states, n_obstacles, obs_xy_radius, obs_z_radius, responsibility, true);
+  const size_t M = n_obstacles > 0 && states ? (size_t)n_obstacles : 0;
+  const std::vector<double> oxy(M, obs_xy_radius), oz(M, obs_z_radius), resp(M, responsibility);
+  return set_obstacles(c, states, (int)M, oxy.data(), oz.data(), resp.data(), true);
 }
 
 int lqro_set_obstacles_device(lqro_ctx* c, const double* d_states, int32_t n_obstacles, double obs_xy_radius,
                               double obs_z_radius, double responsibility) {
-  return set_obstacles(c, d_states, n_obstacles, obs_xy_radius, obs_z_radius, responsibility, false);
+  const size_t M = n_obstacles > 0 && d_states ? (size_t)n_obstacles : 0;
+  const std::vector<double> oxy(M, obs_xy_radius), oz(M, obs_z_radius), resp(M, responsibility);
+  return set_obstacles(c, d_states, (int)M, oxy.data(), oz.data(), resp.data(), false);
 }
 
 int lqro_set_gains(lqro_ctx* c, const double* A, const double* B, const double* L,
@@ -560,9 +596,8 @@ int lqro_set_gains(lqro_ctx* c, const double* A, const double* B, const double* 
   HIPCHK(hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
   LAUNCH(launch_tables(c->stream, (int)na, (int)X, (int)U, g.horizon, c->d_A, c->d_B, c->d_L, c->d_E, per_agent ? 1 : 0,
                        c->d_T, c->d_NCF, c->d_R, c->d_TF, c->pa.rad0, c->pa.rad1, c->pa.rad2, c->umax, c->d_err));
-  if (c->obs_shape)
-    LAUNCH(launch_obs_rtab(c->stream, (int)na, g.horizon, c->d_T, c->d_Ro, c->pa.orad0, c->pa.orad1, c->pa.orad2,
-                           c->pa.oumax));
+  if (c->n_ocls > 0)
+    LAUNCH(launch_obs_rtab(c->stream, c->n_ocls, (int)na, (int)N, g.horizon, c->d_T, c->pa.osc, c->d_Ro));
   int err = 0;
   HIPCHK(hipMemcpyAsync(&err, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -613,8 +648,7 @@ static PairArgs pair_args(const lqro_ctx* c, const StepPlan& plan, const double*
   PairArgs P = c->pa;   // (the LDS layout and the sphere's bounds; the rest zero: no hot list)
   P.N = g.n_agents + c->nobs; P.H = g.horizon; P.NP = g.n_points; P.min_reach = g.min_reach;
   if (c->nobs > 0) {   // (d_x: the context's column array; else obs_jj stays INT_MAX)
-    P.obs_jj = g.n_agents - 1; P.obs_resp = c->obs_resp;
-    P.So = c->obs_shape ? c->d_So : c->d_S; P.Ro = c->obs_shape ? c->d_Ro : c->d_R;
+    P.obs_jj = g.n_agents - 1;   // (the classes' arrays: c->pa, lqro_set_obstacles)
   }
   P.row_begin = c->rb; P.row_stride = c->rs; P.nrows = c->nrows; P.npr = plan.npr;
   P.per_agent = c->per_agent;
@@ -678,7 +712,7 @@ static HullArgs hull_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
   const lqro_config& g = c->cfg;
   HullArgs Hh{};   // (block 0's scratch, no external points: zero)
   Hh.N = g.n_agents + c->nobs; Hh.X = g.x_dim; Hh.H = g.horizon; Hh.NP = g.n_points;
-  if (c->nobs > 0) { Hh.So = P.So; Hh.obs_jj = P.obs_jj; Hh.obs_resp = P.obs_resp; }
+  if (c->nobs > 0) { Hh.So = P.So; Hh.ocls = P.ocls; Hh.oresp = P.oresp; Hh.obs_jj = P.obs_jj; }
   Hh.row_begin = c->rb; Hh.row_stride = c->rs; Hh.npr = plan.npr; Hh.per_agent = c->per_agent;
   Hh.nbr_list = P.nbr_list;
   Hh.r2 = P.r2; Hh.r2_lo = P.r2_lo; Hh.r2_hi = P.r2_hi;
@@ -717,8 +751,8 @@ static HullArgs hull_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
 static ObsSlots obs_slots(const lqro_ctx* c) {
   ObsSlots O{};
   if (c->nobs > 0) {
-    O.on = c->d_cols; O.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;
-    O.jj = c->cfg.n_agents - 1; O.resp = c->obs_resp;
+    O.resp = c->d_oresp; O.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;
+    O.jj = c->cfg.n_agents - 1;
   }
   return O;
 }

@@ -87,6 +87,7 @@ EXPORTS = (
     "lqro_get_stats_ex", "lqro_get_hull_failures", "lqro_get_hull_builds", "lqro_get_qhmerge_pairs",
     "lqro_set_user_planes", "lqro_set_user_planes_device", "lqro_set_fence",
     "lqro_set_obstacles", "lqro_set_obstacles_device",
+    "lqro_set_obstacles_ex", "lqro_set_obstacles_ex_device",
     "lqro_set_hard_planes", "lqro_calculate_new_v_hard",
 )
 # lqro_set_hard_planes' levels: the planes linearProgram4 does not relax
@@ -147,6 +148,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "lqro_set_obstacles"):   # (older libraries in A/B runs lack them)
             L.lqro_set_obstacles.argtypes = [vp, vp, i32, dbl, dbl, dbl]
             L.lqro_set_obstacles_device.argtypes = [vp, vp, i32, dbl, dbl, dbl]
+        if hasattr(L, "lqro_set_obstacles_ex"):
+            L.lqro_set_obstacles_ex.argtypes = [vp, vp, i32, vp, vp, vp]
+            L.lqro_set_obstacles_ex_device.argtypes = [vp, vp, i32, vp, vp, vp]
         if hasattr(L, "lqro_set_hard_planes"):   # (older libraries in A/B runs lack them)
             L.lqro_set_hard_planes.argtypes = [vp, i32]
             L.lqro_calculate_new_v_hard.argtypes = [vp, vp, vp, i32, vp, dbl, vp, i32]
@@ -344,7 +348,7 @@ class Context:
         hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (3,)))
         _check(lib().lqro_set_fence(self._h, _p(lo), _p(hi), float(tau)), "lqro_set_fence")
 
-    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility: float = 1.0):
+    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility=1.0):
         """Obstacles: M columns of every row's pair loop that are not agents
         (lqro_set_obstacles; the reference's commented floor block,
         LQRO:1377-1379, 1421-1434, 752-767).  states: (M, x_dim) — a numpy
@@ -354,30 +358,38 @@ class Context:
         None or M = 0 clears.  xy_radius / z_radius: the obstacles' ellipsoid
         (default: the agents'; (0, 0): a point); responsibility in (0, 1]
         replaces the 0.5 of LQRO:1416 for an obstacle column (1.0: the agent
-        does all the avoiding).  A row then has n_agents - 1 + M records, the
+        does all the avoiding).  Each of the three is a scalar for all the
+        obstacles or a sequence of M, one value per obstacle
+        (lqro_set_obstacles_ex: up to LQRO_OBS_SHAPES_MAX distinct shapes
+        besides the agents').  A row then has n_agents - 1 + M records, the
         obstacle ones with j = n_agents + o.  Changes results against the
         reference."""
-        oxy = self.cfg.xy_radius if xy_radius is None else float(xy_radius)
-        oz = self.cfg.z_radius if z_radius is None else float(z_radius)
         X = self.cfg.x_dim
         if states is None:
-            _check(lib().lqro_set_obstacles(self._h, None, 0, oxy, oz, float(responsibility)), "lqro_set_obstacles")
+            _check(lib().lqro_set_obstacles(self._h, None, 0, self.cfg.xy_radius, self.cfg.z_radius, 1.0),
+                   "lqro_set_obstacles")
             self.n_obstacles, self._obs_keep = 0, None
             return
-        if isinstance(states, np.ndarray) or not hasattr(states, "data_ptr"):
+        dev = not (isinstance(states, np.ndarray) or not hasattr(states, "data_ptr"))
+        if dev:
+            import torch
+            if states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous() or \
+                    states.dim() != 2 or states.shape[1] != X:
+                raise LqroError(f"set_obstacles: need a contiguous float64 device tensor (M, {X})")
+            m = int(states.shape[0])
+            ptr = C.c_void_p(states.data_ptr() if m else None)
+        else:
             st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, X)
-            _check(lib().lqro_set_obstacles(self._h, _p(st), st.shape[0], oxy, oz, float(responsibility)),
-                   "lqro_set_obstacles")
-            self.n_obstacles, self._obs_keep = st.shape[0], None
-            return
-        import torch
-        if states.dtype != torch.float64 or not states.is_cuda or not states.is_contiguous() or \
-                states.dim() != 2 or states.shape[1] != X:
-            raise LqroError(f"set_obstacles: need a contiguous float64 device tensor (M, {X})")
-        m = int(states.shape[0])
-        _check(lib().lqro_set_obstacles_device(self._h, C.c_void_p(states.data_ptr() if m else None), m, oxy, oz,
-                                               float(responsibility)), "lqro_set_obstacles_device")
-        self.n_obstacles, self._obs_keep = m, (states if m else None)
+            m, ptr = st.shape[0], _p(st)
+        per, oxy, oz, resp = obstacle_arrays(m, xy_radius, z_radius, responsibility, self.cfg.xy_radius,
+                                             self.cfg.z_radius)
+        if per:
+            name = "lqro_set_obstacles_ex_device" if dev else "lqro_set_obstacles_ex"
+            _check(getattr(lib(), name)(self._h, ptr, m, _p(oxy), _p(oz), _p(resp)), name)
+        else:
+            name = "lqro_set_obstacles_device" if dev else "lqro_set_obstacles"
+            _check(getattr(lib(), name)(self._h, ptr, m, oxy, oz, resp), name)
+        self.n_obstacles, self._obs_keep = m, (states if dev and m else None)
 
     def set_hard_planes(self, level: int):
         """Which planes linearProgram4 keeps out of its relaxation
@@ -593,6 +605,28 @@ def synthetic_swarm(n: int, x_dim: int = 16, seed: int = SEED, box: float | None
     return x, vg
 
 
+LQRO_OBS_SHAPES_MAX = 8
+
+
+def obstacle_arrays(m: int, xy_radius, z_radius, responsibility, agent_xy: float, agent_z: float):
+    """Context.set_obstacles's three arguments for M obstacles: (False, oxy,
+    oz, resp) as floats when each is a scalar or None (the one-shape call), or
+    (True, oxy, oz, resp) as float64 arrays of M with the scalars broadcast
+    when any is a sequence (lqro_set_obstacles_ex).  A sequence of another
+    length than M raises LqroError."""
+    vals = [agent_xy if xy_radius is None else xy_radius, agent_z if z_radius is None else z_radius,
+            1.0 if responsibility is None else responsibility]
+    if all(np.ndim(v) == 0 for v in vals):
+        return (False, *(float(v) for v in vals))
+    out = []
+    for name, v in zip(("xy_radius", "z_radius", "responsibility"), vals):
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != m):
+            raise LqroError(f"set_obstacles: {name} has {a.shape} values for {m} obstacles")
+        out.append(np.ascontiguousarray(np.broadcast_to(a, (m,))))
+    return (True, *out)
+
+
 def obstacle_states(pos, vel=None, x_dim: int = 16) -> np.ndarray:
     """Hover-trim states for Context.set_obstacles: zeros, then position
     [0..2] and velocity [3..5] (default 0: a static obstacle), and for x_dim =
@@ -751,9 +785,9 @@ class Simulator:
             self.ctx.set_gains(self.A, self.B, Ls[0], Es[0])
         return g
 
-    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility: float = 1.0):
+    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility=1.0):
         """Bodies that are not in qlist as extra columns of every agent's pair
-        loop (Context.set_obstacles); None clears."""
+        loop (Context.set_obstacles: scalars, or one value per obstacle); None clears."""
         self.ctx.set_obstacles(states, xy_radius, z_radius, responsibility)
 
     def set_hard_planes(self, level: int):
@@ -974,9 +1008,10 @@ class DeviceLoop:
     def _sid(self):
         return self.stream.cuda_stream
 
-    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility: float = 1.0):
+    def set_obstacles(self, states, xy_radius=None, z_radius=None, responsibility=1.0):
         """This rank's context takes the obstacle set (every rank the same
-        arguments); a device tensor is read by every later step."""
+        arguments: scalars, or one value per obstacle); a device tensor is
+        read by every later step."""
         self.ctx.set_obstacles(states, xy_radius, z_radius, responsibility)
 
     def set_hard_planes(self, level: int):
