@@ -1854,6 +1854,11 @@ static void sample_gauss(int n, const double* mean, const double* var, const dou
   madd(n, t, mean, out);
 }
 
+void orc_sample_gaussian(int n, const double* mean, const double* var, const double* nrm,
+                         double* out) {
+  sample_gauss(n, mean, var, nrm, out);
+}
+
 /* h (LQRO:399-419) */
 static void obs_h(const double* x, double* z) {
   z[0] = x[9]; z[1] = x[10]; z[2] = x[11];

@@ -158,6 +158,9 @@ void orc_keyframe(double t, const double* xTrue, const double* RTrue, float* out
 /* ---- the per-agent step after the pair loop (LQRO:1437-1446) ----------- */
 /* jacobi (MAT:674-759) on an n x n symmetric matrix (n <= 16). */
 void orc_jacobi(int n, const double* m, double* V, double* D);
+/* sampleGaussian (simulator2.h:21-32), n <= 16; nrm = its n normal() draws. */
+void orc_sample_gaussian(int n, const double* mean, const double* var, const double* nrm,
+                         double* out);
 /* riccatiControllerSteady (LQRO:594-617) -> u (4). */
 void orc_control_velocity(const double* x, const double* R0, const double* vGoal,
                           const double* uGoal, const double* L, const double* E,

@@ -69,10 +69,10 @@ def reflib():
     """The reference's own functions (oracle/_ref/libref.so) or None."""
     global _r
     if _r is None:
-        if not os.path.exists(REF_LIB):
-            if not os.path.isdir(REFERENCE):
-                return None
-            build(ref=True)
+        if os.path.isdir(REFERENCE):
+            build(ref=True)   # (a no-op when libref.so was built from these sources, Makefile)
+        elif not os.path.exists(REF_LIB):
+            return None
         _r = C.CDLL(REF_LIB)
         _r.ref_gjk.restype = C.c_double
     return _r

@@ -24,6 +24,10 @@
 #include <string>
 #include <vector>
 
+/* matrix.h's jacobi (MAT:674-759) calls MSVC's _hypot; glibc's hypot stands in
+ * for it.  Both are correctly rounded on almost every argument; where they
+ * are not, they may differ in the last bit, which no test here can see. */
+#define _hypot hypot
 #include "matrix.h"
 #include "gjk.h"
 #include "Vector3.h"
@@ -50,9 +54,17 @@ static int g_h = 45;
 #define XYRADIUS 0.26
 #define ZRADIUS 0.75
 
+/* normal() (LQRO:340-350) draws from the global rand() stream; here it pops
+ * the caller's draws, so sampleGaussian (simulator2.h:21-32) and propagate
+ * (LQRO:473-486) run on the same normals as the oracle and the kernels. */
+static const double* g_normals = NULL;
+static inline double normal() { return *g_normals++; }
+
 #include "ref_stdafx_helpers.inc"
+#include "ref_sample.inc"
 #include "ref_globals.inc"
 #include "ref_model.inc"
+#include "ref_propagate.inc"
 #include "ref_path.inc"
 
 static void ref_setup_consts() {
@@ -270,12 +282,74 @@ int ref_step(int N, int np, int H, int min_reach, double vmax_reach, const doubl
   return n_inside;
 }
 
+} /* extern "C" */
+
 /* ---- the per-agent step after the pair loop (LQRO:1437-1446) ---------
- * The reference's own controllers and filters.  propagate (LQRO:473-486) and
- * the observation draw (LQRO:1442) call sampleGaussian (simulator2.h:21-32),
- * whose jacobi (MAT:674-759) calls MSVC's _hypot, which this image lacks:
- * they are not built here (the oracle's jacobi is pinned by its properties,
- * tests/test_oracle_dyn.py).  Weights M, N are the reference's (LQRO:1285-1286). */
+ * The reference's own controllers, filters and noise path: jacobi
+ * (MAT:674-759), sampleGaussian (simulator2.h:21-32), propagate
+ * (LQRO:473-486) with the draws supplied, kalmanFilter1 / kalmanFilter2 with
+ * the reference's weights M, N (LQRO:1285-1286) or the caller's.  The one
+ * thing not pinned: MSVC's _hypot against glibc's hypot, last bit (above). */
+
+template <size_t S>
+static void jacobi_n(const double* m_, double* V_, double* D_) {
+  Matrix<S, S> m, V, D;
+  load(m, m_);
+  jacobi(m, V, D);
+  store(V, V_); store(D, D_);
+}
+
+template <size_t S>
+static void sample_n(const double* mean_, const double* var_, const double* normals, double* out_) {
+  Matrix<S> mean; Matrix<S, S> var;
+  load(mean, mean_); load(var, var_);
+  g_normals = normals;
+  store(sampleGaussian(mean, var), out_);
+  g_normals = NULL;
+}
+
+extern "C" {
+
+int ref_jacobi(int n, const double* m, double* V, double* D) {
+  if (n == 3) jacobi_n<3>(m, V, D);
+  else if (n == 6) jacobi_n<6>(m, V, D);
+  else if (n == 16) jacobi_n<16>(m, V, D);
+  else return -1;
+  return 0;
+}
+
+void ref_sample_gaussian6(const double* mean, const double* var, const double* normals, double* out) {
+  sample_n<6>(mean, var, normals, out);
+}
+void ref_sample_gaussian16(const double* mean, const double* var, const double* normals, double* out) {
+  sample_n<16>(mean, var, normals, out);
+}
+
+void ref_propagate(double* x_, double* R_, const double* u_, const double* M_, const double* normals) {
+  ref_setup_consts();
+  State x; Rotation R0; Input u; Matrix<X_DIM, X_DIM> Mw;
+  load(x, x_); load(R0, R_); load(u, u_); load(Mw, M_);
+  g_normals = normals;
+  propagate(x, R0, u, Mw);
+  g_normals = NULL;
+  store(x, x_); store(R0, R_);
+}
+
+void ref_kalman1_m(double* x_, double* R_, const double* u_, const double* M_, double* P_) {
+  ref_setup_consts();
+  State x; Rotation R0; Input u; Matrix<X_DIM, X_DIM> Mw, P;
+  load(x, x_); load(R0, R_); load(u, u_); load(Mw, M_); load(P, P_);
+  kalmanFilter1(x, R0, u, Mw, P);
+  store(x, x_); store(R0, R_); store(P, P_);
+}
+
+void ref_kalman2_n(double* x_, double* R_, const double* z_, const double* N_, double* P_) {
+  ref_setup_consts();
+  State x; Rotation R0; Observation z; Matrix<Z_DIM, Z_DIM> Nw; Matrix<X_DIM, X_DIM> P;
+  load(x, x_); load(R0, R_); load(z, z_); load(Nw, N_); load(P, P_);
+  kalmanFilter2(x, R0, z, Nw, P);
+  store(x, x_); store(R0, R_); store(P, P_);
+}
 
 /* pseudoInverse (MAT:450-477, over jacobi2 MAT:887-1037) of a 16 x 16 matrix,
  * the form controlMatrices applies it in (LQRO:552) */

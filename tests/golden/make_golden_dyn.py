@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/dyn.npz from the REFERENCE's own code.
+"""Generate tests/golden/dyn.npz and dyn_hard.npz from the REFERENCE's own code.
 
 TEST INFRASTRUCTURE.  Runs only in the build container (needs
 oracle/_ref/libref.so, built from /root/reference by oracle/Makefile).  Stores
@@ -13,9 +13,15 @@ inputs and the reference's outputs of the per-agent step after the pair loop:
   quat_*                quatFromRot (stdafx.h:24-33), Quadrotor::visualize's
                         keyframe orientation (LQRO:128-133)
 
-propagate (LQRO:473-486) and the observation draw call sampleGaussian, whose
-jacobi needs MSVC's _hypot (not in this image): they have no fixture; the
-tests pin them through kalmanFilter1 and jacobi's properties.
+and tests/golden/dyn_hard.npz: for the hard families of tests/dyn_cases.py
+(dense noise covariances, large attitudes; 4 or 8 agents each, default model)
+the inputs and the reference's results of one agent step taken function by
+function (tests/dyn_hard.py by_function): findU, propagate (LQRO:473-486),
+kalmanFilter1, the observation draw (sampleGaussian, simulator2.h:21-32),
+kalmanFilter2, findVGoal, sampleGaussian<16> on M itself, and jacobi
+(MAT:674-759) of M and N.  The reference's jacobi is built with glibc's hypot
+in place of MSVC's _hypot (oracle/ref_harness.cpp).  Not written when the
+oracle differs from the reference anywhere.
 
 Usage:  python tests/golden/make_golden_dyn.py
 """
@@ -32,7 +38,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 
 import pyoracle  # noqa: E402
-from dyn_cases import quat_cases, random_agent_cases  # noqa: E402
+import dyn_hard  # noqa: E402
+from dyn_cases import hard_case, quat_cases, random_agent_cases  # noqa: E402
 
 
 def _p(a):
@@ -68,6 +75,26 @@ def main():
                **{"k2_" + k: val for k, val in k2.items()})
     np.savez_compressed(os.path.join(HERE, "dyn.npz"), **out)
     print("wrote dyn.npz:", {k: val.shape for k, val in out.items()})
+    hard(r)
+
+
+def hard(r):
+    g = pyoracle.synthesize()
+    g["l"] = np.array(dyn_hard.L_TERM)
+    out = {}
+    for name in dyn_hard.REF_FAMILIES:
+        cs = hard_case(name, dyn_hard.ref_agents(name))
+        ref = dyn_hard.by_function(dyn_hard.RefFns(r), cs, g)
+        orc = dyn_hard.by_function(dyn_hard.OracleFns(pyoracle), cs, g)
+        for k, val in ref.items():
+            if not (np.all(np.isfinite(val)) and np.array_equal(val.view(np.uint64), orc[k].view(np.uint64))):
+                raise SystemExit(f"{name} {k}: the oracle differs from the reference; nothing written")
+            out[f"{name}/{k}"] = val
+        for k in dyn_hard.REF_INPUTS:
+            out[f"{name}/in_{k}"] = np.ascontiguousarray(cs[k], np.float64)
+    path = os.path.join(HERE, "dyn_hard.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote dyn_hard.npz: {len(dyn_hard.REF_FAMILIES)} families, {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

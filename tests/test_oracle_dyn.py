@@ -1,17 +1,19 @@
 """The oracle's per-agent step after the pair loop (LQRO:1437-1446) against
 the reference: the committed fixture tests/golden/dyn.npz (any machine) and
 the reference's own functions live where oracle/_ref/libref.so exists — all
-bit-exact (both are gcc/glibc builds).  jacobi and sampleGaussian, which the
-reference cannot build here (MSVC _hypot), are pinned by their properties and
-through kalmanFilter1."""
+bit-exact (both are gcc/glibc builds).  The noise path (jacobi, sampleGaussian,
+propagate) is the reference's own code too, with the draws supplied and
+glibc's hypot for MSVC's _hypot (oracle/ref_harness.cpp): on the hard
+families of dyn_cases.py, from tests/golden/dyn_hard.npz and live."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import dyn_hard
 from conftest import GOLDEN
-from dyn_cases import random_agent_cases
+from dyn_cases import hard_case, random_agent_cases
 
 
 def _p(a):
@@ -75,13 +77,22 @@ def test_against_reference_live(oracle, gains):
     r = oracle.reflib()
     if r is None:
         pytest.skip("oracle/_ref/libref.so not available (no /root/reference)")
-    cs = random_agent_cases(40, seed=777)
-    g = dict(gains)
-    g["l"] = np.array([0.01, -0.02, 0.03, -0.04])   # exercise the + l term
-    u, v, k1, k2 = _run_oracle(oracle, g, cs)
     l_ref = np.zeros(4)
     r.ref_gain_l(_p(l_ref))
     _same(l_ref, gains["l"])
+    g = dict(gains)
+    g["l"] = np.array([0.01, -0.02, 0.03, -0.04])   # exercise the + l term
+    _live_compare(oracle, r, g, random_agent_cases(40, seed=777))
+    # large attitudes, rotation errors and rates (asin at and near 1, tilts past
+    # 90 degrees, sinangle == 0 with R != I, errFromRot's r == 0)
+    for name in ("tilt_1.4", "tilt_2.6", "exact", "rot_err", "rates", "quat"):
+        cs = hard_case(name, 16)
+        _live_compare(oracle, r, g, cs)
+        _live_compare(oracle, r, g, dict(cs, x=cs["x_true"], rot=cs["rot_true"]))
+
+
+def _live_compare(oracle, r, g, cs):
+    u, v, k1, k2 = _run_oracle(oracle, g, cs)
     for a in range(cs["x"].shape[0]):
         ur, vr = np.zeros(4), np.zeros(3)
         r.ref_control_velocity(_p(cs["x"][a]), _p(cs["rot"][a]), _p(cs["vgoal"][a]),
@@ -96,6 +107,69 @@ def test_against_reference_live(oracle, gains):
             _same(kk["x"][a], xs)
             _same(kk["rot"][a], rs)
             _same(kk["P"][a], ps)
+
+
+@pytest.fixture(scope="module")
+def gold_hard():
+    return dict(np.load(os.path.join(GOLDEN, "dyn_hard.npz")))
+
+
+def _hard_gains(oracle):
+    g = oracle.synthesize()
+    g["l"] = np.array(dyn_hard.L_TERM)
+    return g
+
+
+@pytest.mark.parametrize("name", dyn_hard.REF_FAMILIES)
+def test_hard_against_golden(oracle, gold_hard, name):
+    """The oracle's noise path, filters and controllers, function by function
+    (dyn_hard.by_function), against the reference's recorded results; and the
+    oracle's whole agent step against that chain."""
+    cs = {k: gold_hard[f"{name}/in_{k}"] for k in dyn_hard.REF_INPUTS}
+    assert cs["x"].shape[0] == dyn_hard.ref_agents(name)
+    g = _hard_gains(oracle)
+    got = dyn_hard.by_function(dyn_hard.OracleFns(oracle), cs, g)
+    for k, val in got.items():
+        _same(val, gold_hard[f"{name}/{k}"])
+    st = dyn_hard.states(cs)
+    u = oracle.agent_step(st, g, cs["nrm"], M=cs["M"], N=cs["N"])
+    for k, ref in dict(u="u", x="k2_x", rot="k2_rot", P="k2_P", x_true="pr_x", rot_true="pr_rot",
+                       vgoal="v").items():
+        _same(u if k == "u" else st[k], gold_hard[f"{name}/{ref}"])
+
+
+@pytest.mark.parametrize("name", dyn_hard.REF_FAMILIES)
+def test_hard_against_reference_live(oracle, name):
+    """The same chain on 16 agents against the reference's functions themselves."""
+    r = oracle.reflib()
+    if r is None:
+        pytest.skip("oracle/_ref/libref.so not available (no /root/reference)")
+    cs = hard_case(name, 16)
+    g = _hard_gains(oracle)
+    got = dyn_hard.by_function(dyn_hard.OracleFns(oracle), cs, g)
+    ref = dyn_hard.by_function(dyn_hard.RefFns(r), cs, g)
+    for k, val in ref.items():
+        assert np.all(np.isfinite(val)), k
+        _same(got[k], val)
+
+
+def test_jacobi_against_reference_live(oracle):
+    """jacobi (MAT:674-759) on dense SPD matrices, n = 16, 6 and 3, from unit
+    scale to 1e-12 (where the DBL_EPSILON cut-off ends the sweeps early)."""
+    r = oracle.reflib()
+    if r is None:
+        pytest.skip("oracle/_ref/libref.so not available (no /root/reference)")
+    from dyn_cases import spd
+    rng = np.random.default_rng(0x4A4143)
+    for n in (16, 6, 3):
+        for scale in (1.0, 1e-4, 1e-9, 1e-12):
+            for _ in range(4):
+                m = spd(n, scale, 1e3, rng)
+                V, D = oracle.jacobi(m)
+                Vr, Dr = np.zeros((n, n)), np.zeros((n, n))
+                assert r.ref_jacobi(n, _p(m), _p(Vr), _p(Dr)) == 0
+                _same(V, Vr)
+                _same(D, Dr)
 
 
 @pytest.mark.parametrize("n,seed", [(16, 1), (6, 2), (3, 3)])
