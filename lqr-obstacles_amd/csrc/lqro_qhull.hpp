@@ -190,10 +190,31 @@ struct QhS : QhTol {
   int findbestnew, notsharp;
   unsigned long long tph[12];   // LQRO_QHULL_PROFILE: cycles per phase
 };
+// The profile build's stamps (scripts/qhull_prof.py on a k_qhull_big run):
+// QHT(k) charges phase k the cycles since the last stamp (tq_, a QhCy of the
+// function); the hooks are what qh_build, qh_one_job and qh_body do with them
 #ifdef LQRO_QHULL_PROFILE
-#define QHT(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); S.tph[k] += t_ - tq_; tq_ = t_; } while (0)
+struct QhCy { unsigned long long t; };
+#define QHT(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); S.tph[k] += t_ - tq_.t; tq_.t = t_; } while (0)
+__device__ __forceinline__ void qh_prof_now(QhCy& c) { c.t = __builtin_amdgcn_s_memtime(); }
+__device__ __forceinline__ void qh_prof_zero(QhS& S) {
+  for (int k = 0; k < 12; k++) S.tph[k] = 0;
+}
+// phase 10: the selection and its commit, since c
+__device__ __forceinline__ void qh_prof_selected(QhS& S, const QhCy& c) { S.tph[10] = __builtin_amdgcn_s_memtime() - c.t; }
+// a job's words added to the step's (prof[11]: the jobs)
+__device__ __forceinline__ void qh_prof_flush(const HullArgs& A, QhS& S, int lane) {
+  S.tph[11] = 1;
+  if (A.prof && lane == 0)
+    for (int k = 0; k < 12; k++) atomicAdd(&A.prof[k], S.tph[k]);
+}
 #else
+struct QhCy {};
 #define QHT(k) do {} while (0)
+__device__ __forceinline__ void qh_prof_now(QhCy&) {}
+__device__ __forceinline__ void qh_prof_zero(QhS&) {}
+__device__ __forceinline__ void qh_prof_selected(QhS&, const QhCy&) {}
+__device__ __forceinline__ void qh_prof_flush(const HullArgs&, QhS&, int) {}
 #endif
 
 // ---- the facet list (poly_r.c: qh_appendfacet, qh_removefacet, qh_prependfacet) ----
@@ -773,10 +794,9 @@ __device__ inline double qh_detsimplex(const QhTol& S, const double* Pr, const i
 
 // qh_qhull on W.Pr[0..n): S holds the final facet list
 __device__ inline void qh_build(const QhW& W, QhS& S, QhL& L, int n, int lane) {
-#ifdef LQRO_QHULL_PROFILE
-  unsigned long long tq_ = __builtin_amdgcn_s_memtime();
-  for (int k = 0; k < 12; k++) S.tph[k] = 0;
-#endif
+  QhCy tq_;
+  qh_prof_now(tq_);
+  qh_prof_zero(S);
   S.status = 0;
   S.nalloc = 1;   // slot 0: the tail sentinel
   S.nfree = 0;
@@ -1373,9 +1393,7 @@ __device__ __forceinline__ QhS qh_one_job(const HullArgs& A, const QhW& W, QhL& 
                                           unsigned long long tjob, int lane) {
   qh_claim_scratch(W, qw_owner(A.qscratch + (size_t)(A.block_base + blockIdx.x) * A.qstride, A.qstride), lane);
   QhS S;
-#ifdef LQRO_QHULL_PROFILE
-  for (int k = 0; k < 12; k++) S.tph[k] = 0;
-#endif
+  qh_prof_zero(S);
   S.status = 0;
   S.nalloc = 1;
   S.nins = 0;
@@ -1383,16 +1401,13 @@ __device__ __forceinline__ QhS qh_one_job(const HullArgs& A, const QhW& W, QhL& 
   if (L.fail || n < 4) S.status = QHS_INPUT;
   else qh_build(W, S, L, n, lane);
   hl_sync();
-#ifdef LQRO_QHULL_PROFILE
-  const unsigned long long tq_ = __builtin_amdgcn_s_memtime();
-#endif
+  QhCy tq_;
+  qh_prof_now(tq_);
   // (qh_select is out of line: a copy, or the whole job is kept in scratch for J.vrel's sake)
   const double vrel[3] = {J.vrel[0], J.vrel[1], J.vrel[2]};
   qh_select(A, W, S, lane, J.xi, vrel, slot);
   if (lane == 0) hull_build_note(A, slot, 1, tjob, n, S.nins, S.nalloc - 1);
-#ifdef LQRO_QHULL_PROFILE
-  S.tph[10] = __builtin_amdgcn_s_memtime() - tq_;
-#endif
+  qh_prof_selected(S, tq_);
   return S;
 }
 
@@ -1409,11 +1424,7 @@ __device__ inline void qh_body(const HullArgs& A, QhL& L, bool retryq) {
     const HullJob J = hull_job(A, slot);
     const int n = hull_points(A, L, J.Ti, J.Ni, J.xi, J.xj, J.vrel, W.Pr, W.Pf);
     QhS S = qh_one_job(A, W, L, J, n, slot, tjob, lane);
-#ifdef LQRO_QHULL_PROFILE
-    S.tph[11] = 1;
-    if (A.prof && lane == 0)
-      for (int k = 0; k < 12; k++) atomicAdd(&A.prof[k], S.tph[k]);
-#endif
+    qh_prof_flush(A, S, lane);
     if (A.ext_nf && lane == 0) *A.ext_nf = S.status;   // test hook: the build's status bits
     if (A.ext_facets && lane == 0) {                     // test hook: the facet list, Fv order
       int k = 0;

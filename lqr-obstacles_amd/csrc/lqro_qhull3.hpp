@@ -772,11 +772,14 @@ __device__ __forceinline__ void q3_st_rel_lds(int* p, int v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 // wait (bounded) until *p != v (ne) or == v (!ne); the last value read
-__device__ __forceinline__ int q3_wait(const int* p, int v, bool ne) {
+// (wp: the profile build's probe of wave 0's wait for a speculation)
+__device__ __forceinline__ int q3_wait(const int* p, int v, bool ne, Q3WaitProf* wp = nullptr) {
   int x = q3_ld_acq(p);
+  if (wp) wp->first();   // the first read back
   for (long w = 0; (ne ? x == v : x != v) && w < (1l << 24); ++w) {
     __builtin_amdgcn_s_sleep(Q3_W0_SLEEP);
     x = q3_ld_acq(p);
+    if (wp) wp->spin();
   }
   return x;
 }
@@ -817,9 +820,8 @@ __device__ inline bool q3_help(const Q3W& W, Q3L& L, int lane, const Q3Col& C) {
     if (!got) __hip_atomic_fetch_add(&L.hbusy, -1, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
   if (!__builtin_amdgcn_readfirstlane(got)) return false;
-#ifdef LQRO_QHULL_LONGPROF
-  const unsigned long long th0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  Q3Rt th0, th1;
+  q3_rt_now(th0);
   Q3S S;
   S.MINvisible = L.c_dist[0]; S.MAXcoplanar = L.c_dist[1]; S.DISTround = L.c_dist[2];
   S.MINoutside = 2 * S.MINvisible;
@@ -833,9 +835,7 @@ __device__ inline bool q3_help(const Q3W& W, Q3L& L, int lane, const Q3Col& C) {
   const int from = L.hq_from, np = L.hq_np, pos = 64 * k + lane;
   q3_chunk_locate<true>(W, S, L, 64 * k, from, np, L.hq_sharp, L.hq_init != 0, lane, pre, 0, -1, pt, f, d, isout,
                         trig, ls, C);
-#ifdef LQRO_QHULL_LONGPROF
-  const unsigned long long th1 = __builtin_amdgcn_s_memrealtime();
-#endif
+  q3_rt_now(th1);
   // what wave 0 does with each result (q3_locate_seq), under the same state:
   // the event kind and the destination (a new facet's index; an old facet's
   // is wave 0's to give)
@@ -860,12 +860,7 @@ __device__ inline bool q3_help(const Q3W& W, Q3L& L, int lane, const Q3Col& C) {
     L.hr_ls[b] = st;
     q3_st_rel_lds(&L.hr_st[b], k + 1);   // (the results are in LDS)
     __hip_atomic_fetch_add(&L.hbusy, -1, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef LQRO_QHULL_LONGPROF
-    const unsigned long long th2 = __builtin_amdgcn_s_memrealtime();
-    atomicAdd(&L.hprof[0], 1ull);
-    atomicAdd(&L.hprof[1], th1 - th0);
-    atomicAdd(&L.hprof[2], th2 - th0);
-#endif
+    q3_lp_helped(L, th0, th1);
   }
   return true;
 }
@@ -903,6 +898,7 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
   const bool a2 = help && sharp == 1 && (L.qflags & 64);
   bool ahead = false;   // the current post's state is the one the trigger leads to
   const Q3Col C0 = q3_col0(L, lane);
+  Q3Rt tw0, ts0;   // (diagnostics) a wait for a helper's chunk, a stop of the helpers: their starts
   auto post = [&](int from2) {   // (no helper holds a claim: hctl = 0, hbusy = 0)
     S.hgen = S.hgen % 32767 + 1;
     ahead = a2 && !S.findbestnew;
@@ -967,18 +963,12 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
                                                        __HIP_MEMORY_SCOPE_WORKGROUP);
           }
           mine = __builtin_amdgcn_readfirstlane(m) != 0;
-#ifdef LQRO_QHULL_LONGPROF
-          const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
-#endif
+          q3_rt_now(tw0);
           if (!mine && own) { mine = true; held = b; }
           if (!mine) st = q3_wait(&L.hr_st[b], k + 1, false);
-#ifdef LQRO_QHULL_LONGPROF
-          if (!mine) S.pf.lp_hwait += __builtin_amdgcn_s_memrealtime() - tw0;
-#endif
+          q3_lp_hwait(S.pf, tw0, !mine);
         }
-#ifdef LQRO_QHULL_LONGPROF
-        if (mine) S.pf.lp_own++; else S.pf.lp_got++;
-#endif
+        q3_lp_chunk(S.pf, mine);
         int kv = 0;
         if (!mine) {
           if (st != k + 1) { S.status |= QHS_CAPACITY | QHS_TIMEOUT; break; }
@@ -1067,17 +1057,9 @@ __device__ inline void q3_locate_seq(const Q3W& W, Q3S& S, Q3L& L, int np, int s
       posted = true;
       continue;
     }
-#ifdef LQRO_QHULL_LONGPROF
-    const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    q3_rt_now(ts0);
     if (help) stop();   // (the rest, if any, is posted again under the new state)
-#ifdef LQRO_QHULL_LONGPROF
-    if (help) {
-      S.pf.lp_stop += __builtin_amdgcn_s_memrealtime() - ts0;
-      S.pf.lp_posts++;
-      if (ev_pos < np) S.pf.lp_ev++;
-    }
-#endif
+    q3_lp_stopped(S.pf, ts0, help, ev_pos < np);
     if (S.status & QHS_CAPACITY) return;
     if (ev_pos < np) {
       Q3C(24, 1);
@@ -1590,10 +1572,8 @@ __device__ inline void q3_spec(const Q3W& W, Q3L& L, int lane, unsigned short ep
   Q.one = 0;
   Q.rt = -1;
   W1T(1);
-#ifdef LQRO_QHULL_LONGPROF
-  const unsigned long long tq0_ = __builtin_amdgcn_s_memrealtime();
-  int reloads_ = 0;
-#endif
+  Q3ScanProf SP;
+  q3_lp_scan_begin(SP);
   int ok = 0;
   // 1. the queue's next live facet with points (not one insertion k made visible)
   const int qt = L.pub_qtail;
@@ -1632,9 +1612,7 @@ __device__ inline void q3_spec(const Q3W& W, Q3L& L, int lane, unsigned short ep
   Q.pc_from = -1;
   for (int qh = qh0; facet < 0 && qh < qt;) {
     if (qh >= Q.qcb + Q.qcn || qh < Q.qcb) {
-#ifdef LQRO_QHULL_LONGPROF
-      ++reloads_;
-#endif
+      q3_lp_scan_reload(SP);
       Q.qcb = qh;
       Q.qcn = min(64, qt - qh);
       if (lane < Q.qcn) {
@@ -1671,10 +1649,7 @@ __device__ inline void q3_spec(const Q3W& W, Q3L& L, int lane, unsigned short ep
   }
   int ls = 0, nvis = 0, nnew = 0, ts = 0, lm = 0;
   W1T(2);
-#ifdef LQRO_QHULL_LONGPROF
-  const unsigned long long tq1_ = __builtin_amdgcn_s_memrealtime();
-  if (lane == 0) { L.hprof[8] += (unsigned long long)reloads_; L.hprof[9] += tq1_ - tq0_; }
-#endif
+  q3_lp_scan_end(L, SP, lane);
   if (facet >= 0) {
     // 2. qh_findhorizon, as wave 0's (level order, first occurrence), visits as epochs
     if (lane == 0) L.sp_visf[0] = facet;
@@ -1724,13 +1699,9 @@ __device__ inline void q3_spec(const Q3W& W, Q3L& L, int lane, unsigned short ep
       }
       lo = hi;
       if (nvis > Q3_VISCAP) cap = true;
-#ifdef LQRO_QHULL_PROFILE
-      P.t[11] += 1;
-#endif
+      W1C(11, 1);
     }
-#ifdef LQRO_QHULL_LONGPROF
-    if (lane == 0) L.hprof[10] += __builtin_amdgcn_s_memrealtime() - tq1_;
-#endif
+    q3_lp_horizon_end(L, SP, lane);
     // the horizon to wave 2, which fetches the partition sequence's head
     if (!cap && lane == 0) {
       L.sp_hnvis = nvis;
@@ -2006,9 +1977,7 @@ __device__ inline void q3_prefetch(const Q3W& W, Q3L& L, int lane, int p) {
 // qh_qhull on W.Pr[0..n) (qconvex's defaults; lqro_qhull.hpp qh_build step
 // for step)
 __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
-#ifdef LQRO_QHULL_PROFILE
-  S.pf.tq = __builtin_amdgcn_s_memtime();
-#endif
+  q3_prof_stamp(S.pf);
   const unsigned long long ltmask = (1ull << lane) - 1ull;
   S.status = 0;
   S.nalloc = 1;
@@ -2249,10 +2218,6 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
   unsigned qk = 0;
   double qx = 0.0, qy = 0.0, qz = 0.0;
   for (;;) {
-#ifdef LQRO_QHULL_PROFILE
-    unsigned long long snap_[21];
-    for (int k = 0; k < 21; k++) snap_[k] = S.pf.tph[k];
-#endif
     // qh_nextfurthest: the first queued facet still alive (same key) with
     // points
     int facet = -1, furthest = -1;
@@ -2269,53 +2234,12 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
     pre.q = -1;
     pre.pad = 0;
     int pfa = 0, pfnp = -1;
-#ifdef LQRO_QHULL_LONGPROF
-    const unsigned long long lp_ta = __builtin_amdgcn_s_memrealtime();
-    S.pf.lp_tail += S.pf.lp_tw ? lp_ta - S.pf.lp_tw : 0ull;
-#endif
+    Q3InsProf IP;
+    q3_prof_ins_begin(S.pf, IP);
     if (phase > 0) {
-#ifdef LQRO_QHULL_PROFILE
-      const unsigned long long tw_ = __builtin_amdgcn_s_memtime();
-#endif
-#ifdef LQRO_QHULL_PROFILE
-      int spins_ = 0;
-      int dn = q3_ld_acq(&L.sp_done);
-      const unsigned long long tf_ = __builtin_amdgcn_s_memtime();   // the first read back
-      for (long w = 0; dn != phase && w < (1l << 24); ++w) {
-        __builtin_amdgcn_s_sleep(Q3_W0_SLEEP);
-        dn = q3_ld_acq(&L.sp_done);
-        ++spins_;
-      }
-      if (S.pf.prev1) { S.pf.tfr += tf_ - tw_; S.pf.nsp += (unsigned long long)spins_; }
-#else
-      const int dn = q3_wait(&L.sp_done, phase, false);
-#endif
-#ifdef LQRO_QHULL_LONGPROF
-      {   // (wave 0 waited: the speculation's end -> seen here)
-        const unsigned long long tn = __builtin_amdgcn_s_memrealtime();
-        const unsigned long long de = q3_lds(L.lp_doner);
-        if (tn - lp_ta > 20 && tn > de && lane == 0) { L.hprof[6] += tn - de; L.hprof[7] += 1; }
-      }
-#endif
-#ifdef LQRO_QHULL_PROFILE
-      {
-        const unsigned long long tn_ = __builtin_amdgcn_s_memtime();
-        S.pf.tw += tn_ - tw_;
-        S.pf.nw += 1;
-        if (tn_ - tw_ > 200) S.pf.tdl += tn_ - L.done_t;   // (waited) speculation end -> seen here
-        S.pf.tseen = tn_;
-        if (S.pf.prev1) {   // after a one-chunk insertion: its wait, publication -> speculation end / -> seen
-          S.pf.tw1 += tn_ - tw_; S.pf.nw1 += 1;
-          S.pf.tse += L.done_t - L.pub_t; S.pf.tsn += tn_ - L.pub_t;
-          S.pf.tfr2 += L.done_t2 - L.pub_t;
-          const unsigned long long nr_ = __builtin_amdgcn_s_memrealtime();
-          S.pf.r_start += L.start_r - L.pub_r; S.pf.r_done += L.done_r - L.pub_r; S.pf.r_seen += nr_ - L.pub_r;
-        }
-      }
-#endif
-#ifdef LQRO_QHULL_LONGPROF
-      S.pf.lp_wait += __builtin_amdgcn_s_memrealtime() - lp_ta;
-#endif
+      q3_prof_wait_begin(IP);
+      const int dn = q3_wait(&L.sp_done, phase, false, &IP.wp);
+      q3_prof_wait_end(S.pf, L, IP, lane);
       if (dn != phase) {   // wave 1 still speculating (it writes vertex records from L.nslot): stop
         S.status |= QHS_CAPACITY | QHS_TIMEOUT;
         return;
@@ -2481,9 +2405,7 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
       S.qhead = qcb + qcn;
     }
     Q3T(1);
-#ifdef LQRO_QHULL_PROFILE
-    const unsigned long long tins_ = S.pf.tq;   // this insertion's start (for the long-sequence split)
-#endif
+    q3_prof_ins_chosen(S.pf, IP);
     if (furthest < 0) {
       // the build is done: the selection reads vertex records wave 1 wrote
       if (phase > 0 && q3_wait(&L.sp_gdone, phase, false) != phase) S.status |= QHS_CAPACITY | QHS_TIMEOUT;
@@ -2806,20 +2728,9 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
       L.pub_nnew = nnew;
     }
     ++phase;
-#ifdef LQRO_QHULL_PROFILE
-    if (lane == 0) { L.pub_t = __builtin_amdgcn_s_memtime(); L.pub_r = __builtin_amdgcn_s_memrealtime(); }
-    // (this wave's clock) seen -> publication
-    if (S.pf.tseen) { S.pf.tpre += __builtin_amdgcn_s_memtime() - S.pf.tseen; S.pf.npre += 1; }
-#endif
-#ifdef LQRO_QHULL_LONGPROF
-    const unsigned long long lp_t0 = __builtin_amdgcn_s_memrealtime();
-    S.pf.lp_adopt += lp_t0 - lp_ta;   // (less the wait, in lp_wait)
-    if (lane == 0) L.lp_pubr = lp_t0;
-#endif
+    q3_prof_publish(S.pf, L, IP, lane);
     if (lane == 0) q3_st_rel(&L.ph, phase);
-#ifdef LQRO_QHULL_PROFILE
-    if (lane == 0) S.pf.trel += __builtin_amdgcn_s_memtime() - L.pub_t;   // the release's own cost
-#endif
+    q3_prof_published(S.pf, L, lane);
     S.findbestnew = 0;
     S.notsharp = 0;
     S.nmov = 0;
@@ -2853,21 +2764,12 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
       double rd;
       HullPt rpt;
       q3_locate_seq(W, S, L, np2, sharp, false, lane, pre, prestart, true, rg, rd, rpt);
-#ifdef LQRO_QHULL_LONGPROF
-      if (np2 > 64) S.pf.lp_tloc += __builtin_amdgcn_s_memrealtime() - lp_t0;
-#endif
+      q3_lp_located(S.pf, IP, np2);
       Q3T(6);
       q3_emit_seq(W, S, L, np2, nnew, false, lane, rg, rd, rpt);
       Q3T(7);
     }
-#ifdef LQRO_QHULL_LONGPROF
-    {
-      const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - lp_t0;
-      S.pf.lp_all += dt;
-      if (np2 > 64) { S.pf.lp_n += 1; S.pf.lp_pts += (unsigned long long)np2; S.pf.lp_t += dt; }
-      S.pf.lp_tw = lp_t0 + dt;
-    }
-#endif
+    q3_lp_partitioned(S.pf, IP, np2);
     if (S.status & QHS_CAPACITY) return;
     // deleted vertices (a visible facet's vertex on no new facet) close to a
     // new facet: Qhull's qh_partitioncoplanar would act (not restated).  The
@@ -2911,15 +2813,7 @@ __device__ inline void q3_build(const Q3W& W, Q3S& S, Q3L& L, int n, int lane) {
     S.notsharp = 0;
     hl_sync();
     Q3T(9);
-#ifdef LQRO_QHULL_PROFILE
-    // insertions whose partition sequence is longer than one chunk: 29 cycles, 30 count
-    S.pf.prev1 = np2 <= 64;
-    if (np2 > 64) { S.pf.tph[29] += S.pf.tq - tins_; S.pf.tph[30] += 1; }
-    else {
-      for (int k = 0; k < 21; k++) S.pf.tps[k] += S.pf.tph[k] - snap_[k];
-      S.pf.nps += 1;
-    }
-#endif
+    q3_prof_ins_end(S.pf, IP, np2);
   }
 }
 
@@ -3185,49 +3079,24 @@ __device__ __forceinline__ void q3_body(const HullArgs& A, Q3L& L, QhL* LB = nul
           last = p;
           ++ep;
           ++ep2;
-#ifdef LQRO_QHULL_PROFILE
-          const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-          P.tq = t0_;
-          P.t[14] += t0_ - L.pub_t;   // publication -> speculation start
-          if (P.tq2) P.t[15] += t0_ - P.tq2;   // (this wave's clock) its last speculation's end -> this start
-          if (lane == 0) L.start_r = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef LQRO_QHULL_LONGPROF
-          const unsigned long long ts_ = __builtin_amdgcn_s_memrealtime();
-#endif
+          Q3Cy t0;
+          Q3Rt ts;
+          q3_prof_spec_begin(L, P, t0, ts, lane);
           q3_spec(W, L, lane, ep, ep2, Q, P, p);
           hl_sync();
-#ifdef LQRO_QHULL_LONGPROF
-          if (lane == 0) {
-            const unsigned long long te_ = __builtin_amdgcn_s_memrealtime();
-            L.hprof[3] += 1; L.hprof[4] += ts_ - q3_lds(L.lp_pubr); L.hprof[5] += te_ - ts_;
-            L.lp_doner = te_;
-          }
-#endif
-#ifdef LQRO_QHULL_PROFILE
-          if (lane == 0) L.done_t = __builtin_amdgcn_s_memtime();
-#endif
+          q3_prof_spec_done(L, ts, lane);
           if (lane == 0) q3_st_rel_lds(&L.sp_done, p);
           if (lane == 0) q3_st_rel(&L.sp_gdone, p);
           if (L.qflags & 4) q3_prescan(W, L, lane, ep, ep2, Q);
-#ifdef LQRO_QHULL_PROFILE
-          if (lane == 0) { L.done_t2 = __builtin_amdgcn_s_memtime(); L.done_r = __builtin_amdgcn_s_memrealtime(); }
-          P.tq2 = __builtin_amdgcn_s_memtime();
-          P.t[0] += __builtin_amdgcn_s_memtime() - t0_;
-          P.t[7] += 1;
-#endif
+          q3_prof_spec_end(L, P, t0, lane);
           idle = 0;
           continue;
         }
         {
-#ifdef LQRO_QHULL_PROFILE
-          const unsigned long long t0_ = __builtin_amdgcn_s_memtime();
-#endif
+          Q3Cy t0;
+          q3_cy_now(t0);
           if (q3_help(W, L, lane, CH)) {   // a posted chunk
-#ifdef LQRO_QHULL_PROFILE
-            P.t[6] += __builtin_amdgcn_s_memtime() - t0_;
-            P.t[8] += 1;
-#endif
+            q3_prof_w1_helped(P, t0);
             idle = 0;
             continue;
           }

@@ -1,7 +1,11 @@
 // lqro_qhull3_prof.hpp — k_qhull's diagnostics (lqro_qhull3.hpp), in one
 // place: the profile-only state of a build (Q3Prof, a member of Q3S; empty in
-// the plain build), the stamp macros the hot functions use (Q3T, W1T, Q3C)
-// and what q3_body does with them at a job's start and end.  Two diagnostic
+// the plain build), the stamp macros the hot functions use (Q3T, W1T, Q3C,
+// W1C), the diagnostic locals of an insertion, a wait and a queue scan
+// (Q3InsProf, Q3WaitProf, Q3ScanProf, the stamps Q3Cy / Q3Rt) and the named
+// hooks the hot functions call: a hook's body is behind the #ifdef here, its
+// call site in lqro_qhull3.hpp is not, so the algorithm reads without them
+// and the plain build compiles to the same kernels.  Two diagnostic
 // builds (scripts/build_variant.sh): LQRO_QHULL_PROFILE (cycles per phase,
 // scripts/qhull_prof.py; with LQRO_QHULL_PROF_LIGHT the stamps do not drain
 // the memory queue) and LQRO_QHULL_LONGPROF (the long partitions of each
@@ -86,9 +90,72 @@ struct Q3P {
 #endif
 #ifdef LQRO_QHULL_PROFILE
 #define Q3C(k, v) do { S.pf.tph[k] += (unsigned long long)(v); } while (0)
+#define W1C(k, v) do { P.t[k] += (unsigned long long)(v); } while (0)   // wave 1's counters (11: horizon levels)
 #else
 #define Q3C(k, v) do {} while (0)
+#define W1C(k, v) do {} while (0)
 #endif
+
+// a stamp a hook below takes and a later one reads: cycles (LQRO_QHULL_PROFILE)
+// and the 100 MHz real time (LQRO_QHULL_LONGPROF)
+struct Q3Cy {
+#ifdef LQRO_QHULL_PROFILE
+  unsigned long long t;
+#endif
+};
+struct Q3Rt {
+#ifdef LQRO_QHULL_LONGPROF
+  unsigned long long t;
+#endif
+};
+__device__ __forceinline__ void q3_cy_now(Q3Cy& c) {
+#ifdef LQRO_QHULL_PROFILE
+  c.t = __builtin_amdgcn_s_memtime();
+#endif
+}
+__device__ __forceinline__ void q3_rt_now(Q3Rt& r) {
+#ifdef LQRO_QHULL_LONGPROF
+  r.t = __builtin_amdgcn_s_memrealtime();
+#endif
+}
+
+// q3_wait's probe, for wave 0's wait for a speculation: the time of the
+// first read back and the reads after it
+struct Q3WaitProf {
+#ifdef LQRO_QHULL_PROFILE
+  unsigned long long tf;
+  int spins;
+#endif
+  __device__ __forceinline__ void first() {
+#ifdef LQRO_QHULL_PROFILE
+    tf = __builtin_amdgcn_s_memtime();
+#endif
+  }
+  __device__ __forceinline__ void spin() {
+#ifdef LQRO_QHULL_PROFILE
+    ++spins;
+#endif
+  }
+};
+
+// wave 0's profile-only words of one insertion (q3_build's loop)
+struct Q3InsProf {
+#ifdef LQRO_QHULL_PROFILE
+  unsigned long long snap[21];   // Q3Prof::tph at its start
+  unsigned long long tins;       // its start (for the long-sequence split)
+#endif
+  Q3Cy tw;         // the wait for the speculation begins
+  Q3WaitProf wp;
+  Q3Rt ta, t0;     // its start, its publication
+};
+
+// wave 1's profile-only words of one queue scan and horizon (q3_spec)
+struct Q3ScanProf {
+  Q3Rt t0, t1;     // the scan's start and end
+#ifdef LQRO_QHULL_LONGPROF
+  int reloads;     // queue-window reloads
+#endif
+};
 
 // wave 0, before a job's build: its words zeroed
 __device__ __forceinline__ void q3_prof_begin(Q3Prof& F) {
@@ -114,7 +181,8 @@ __device__ __forceinline__ void q3_prof_begin(Q3Prof& F) {
 #endif
 }
 
-// wave 0, before the selection: the stamp phase 10 (q3_prof_flush) counts from
+// wave 0, at q3_build's start and before the selection: the stamp the next
+// Q3T, or phase 10 (q3_prof_flush), counts from
 __device__ __forceinline__ void q3_prof_stamp(Q3Prof& F) {
 #ifdef LQRO_QHULL_PROFILE
   F.tq = __builtin_amdgcn_s_memtime();
@@ -202,6 +270,220 @@ __device__ __forceinline__ void q3_longprof_flush(const HullArgs& A, int k, cons
     r[14] = L.hprof[0]; r[15] = L.hprof[1] | (L.hprof[2] << 32);
     for (int q = 3; q < 11; q++) r[13 + q] = L.hprof[q];   // r[16..23]
   }
+#endif
+}
+
+// ---- the hooks of the hot functions, in the order they are met ----
+// (LT: Q3L, defined after this header; its diagnostic members are read from
+// LDS by name of the address space, as q3_lds does)
+#define Q3_PROF_LDS(r) (*(const __attribute__((address_space(3))) unsigned long long*)(&(r)))
+
+// q3_help, lane 0, its chunk released: claimed at t0, located by t1
+template <class LT>
+__device__ __forceinline__ void q3_lp_helped(LT& L, const Q3Rt& t0, const Q3Rt& t1) {
+#ifdef LQRO_QHULL_LONGPROF
+  const unsigned long long th2 = __builtin_amdgcn_s_memrealtime();
+  atomicAdd(&L.hprof[0], 1ull);
+  atomicAdd(&L.hprof[1], t1.t - t0.t);
+  atomicAdd(&L.hprof[2], th2 - t0.t);
+#endif
+}
+
+// q3_locate_seq: wave 0 waited (or not) since tw0 for a helper's chunk
+__device__ __forceinline__ void q3_lp_hwait(Q3Prof& F, const Q3Rt& tw0, bool waited) {
+#ifdef LQRO_QHULL_LONGPROF
+  if (waited) F.lp_hwait += __builtin_amdgcn_s_memrealtime() - tw0.t;
+#endif
+}
+// a chunk of a helped sequence: located by wave 0 (mine) or taken from a helper
+__device__ __forceinline__ void q3_lp_chunk(Q3Prof& F, bool mine) {
+#ifdef LQRO_QHULL_LONGPROF
+  if (mine) F.lp_own++; else F.lp_got++;
+#endif
+}
+// a helped sequence's helpers stopped (since ts0) after a post; ev: by an event
+__device__ __forceinline__ void q3_lp_stopped(Q3Prof& F, const Q3Rt& ts0, bool help, bool ev) {
+#ifdef LQRO_QHULL_LONGPROF
+  if (help) {
+    F.lp_stop += __builtin_amdgcn_s_memrealtime() - ts0.t;
+    F.lp_posts++;
+    if (ev) F.lp_ev++;
+  }
+#endif
+}
+
+// q3_spec: the queue scan begins, reloads its window, ends; the horizon ends
+__device__ __forceinline__ void q3_lp_scan_begin(Q3ScanProf& C) {
+  q3_rt_now(C.t0);
+#ifdef LQRO_QHULL_LONGPROF
+  C.reloads = 0;
+#endif
+}
+__device__ __forceinline__ void q3_lp_scan_reload(Q3ScanProf& C) {
+#ifdef LQRO_QHULL_LONGPROF
+  ++C.reloads;
+#endif
+}
+template <class LT>
+__device__ __forceinline__ void q3_lp_scan_end(LT& L, Q3ScanProf& C, int lane) {
+  q3_rt_now(C.t1);
+#ifdef LQRO_QHULL_LONGPROF
+  if (lane == 0) { L.hprof[8] += (unsigned long long)C.reloads; L.hprof[9] += C.t1.t - C.t0.t; }
+#endif
+}
+template <class LT>
+__device__ __forceinline__ void q3_lp_horizon_end(LT& L, const Q3ScanProf& C, int lane) {
+#ifdef LQRO_QHULL_LONGPROF
+  if (lane == 0) L.hprof[10] += __builtin_amdgcn_s_memrealtime() - C.t1.t;
+#endif
+}
+
+// q3_build, an insertion begins: the phases so far; the tail since the last partition
+__device__ __forceinline__ void q3_prof_ins_begin(Q3Prof& F, Q3InsProf& I) {
+#ifdef LQRO_QHULL_PROFILE
+  for (int k = 0; k < 21; k++) I.snap[k] = F.tph[k];
+#endif
+  q3_rt_now(I.ta);
+#ifdef LQRO_QHULL_LONGPROF
+  F.lp_tail += F.lp_tw ? I.ta.t - F.lp_tw : 0ull;
+#endif
+}
+// before wave 0's wait for the speculation (q3_wait with I.wp)
+__device__ __forceinline__ void q3_prof_wait_begin(Q3InsProf& I) {
+  q3_cy_now(I.tw);
+#ifdef LQRO_QHULL_PROFILE
+  I.wp.spins = 0;
+#endif
+}
+// and after it
+template <class LT>
+__device__ __forceinline__ void q3_prof_wait_end(Q3Prof& F, LT& L, const Q3InsProf& I, int lane) {
+#ifdef LQRO_QHULL_PROFILE
+  if (F.prev1) { F.tfr += I.wp.tf - I.tw.t; F.nsp += (unsigned long long)I.wp.spins; }
+#endif
+#ifdef LQRO_QHULL_LONGPROF
+  {   // (wave 0 waited: the speculation's end -> seen here)
+    const unsigned long long tn = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long de = Q3_PROF_LDS(L.lp_doner);
+    if (tn - I.ta.t > 20 && tn > de && lane == 0) { L.hprof[6] += tn - de; L.hprof[7] += 1; }
+  }
+#endif
+#ifdef LQRO_QHULL_PROFILE
+  {
+    const unsigned long long tn_ = __builtin_amdgcn_s_memtime();
+    F.tw += tn_ - I.tw.t;
+    F.nw += 1;
+    if (tn_ - I.tw.t > 200) F.tdl += tn_ - L.done_t;   // (waited) speculation end -> seen here
+    F.tseen = tn_;
+    if (F.prev1) {   // after a one-chunk insertion: its wait, publication -> speculation end / -> seen
+      F.tw1 += tn_ - I.tw.t; F.nw1 += 1;
+      F.tse += L.done_t - L.pub_t; F.tsn += tn_ - L.pub_t;
+      F.tfr2 += L.done_t2 - L.pub_t;
+      const unsigned long long nr_ = __builtin_amdgcn_s_memrealtime();
+      F.r_start += L.start_r - L.pub_r; F.r_done += L.done_r - L.pub_r; F.r_seen += nr_ - L.pub_r;
+    }
+  }
+#endif
+#ifdef LQRO_QHULL_LONGPROF
+  F.lp_wait += __builtin_amdgcn_s_memrealtime() - I.ta.t;
+#endif
+}
+// the insertion's point is chosen (after Q3T(1))
+__device__ __forceinline__ void q3_prof_ins_chosen(const Q3Prof& F, Q3InsProf& I) {
+#ifdef LQRO_QHULL_PROFILE
+  I.tins = F.tq;
+#endif
+}
+// before the publication to wave 1 (the release of L.ph) ...
+template <class LT>
+__device__ __forceinline__ void q3_prof_publish(Q3Prof& F, LT& L, Q3InsProf& I, int lane) {
+#ifdef LQRO_QHULL_PROFILE
+  if (lane == 0) { L.pub_t = __builtin_amdgcn_s_memtime(); L.pub_r = __builtin_amdgcn_s_memrealtime(); }
+  // (this wave's clock) seen -> publication
+  if (F.tseen) { F.tpre += __builtin_amdgcn_s_memtime() - F.tseen; F.npre += 1; }
+#endif
+  q3_rt_now(I.t0);
+#ifdef LQRO_QHULL_LONGPROF
+  F.lp_adopt += I.t0.t - I.ta.t;   // (less the wait, in lp_wait)
+  if (lane == 0) L.lp_pubr = I.t0.t;
+#endif
+}
+// ... and after it: the release's own cost
+template <class LT>
+__device__ __forceinline__ void q3_prof_published(Q3Prof& F, const LT& L, int lane) {
+#ifdef LQRO_QHULL_PROFILE
+  if (lane == 0) F.trel += __builtin_amdgcn_s_memtime() - L.pub_t;
+#endif
+}
+// the partition sequence (np points) is located
+__device__ __forceinline__ void q3_lp_located(Q3Prof& F, const Q3InsProf& I, int np) {
+#ifdef LQRO_QHULL_LONGPROF
+  if (np > 64) F.lp_tloc += __builtin_amdgcn_s_memrealtime() - I.t0.t;
+#endif
+}
+// and emitted (or empty)
+__device__ __forceinline__ void q3_lp_partitioned(Q3Prof& F, const Q3InsProf& I, int np) {
+#ifdef LQRO_QHULL_LONGPROF
+  const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - I.t0.t;
+  F.lp_all += dt;
+  if (np > 64) { F.lp_n += 1; F.lp_pts += (unsigned long long)np; F.lp_t += dt; }
+  F.lp_tw = I.t0.t + dt;
+#endif
+}
+// the insertion is over: those whose partition sequence is longer than one
+// chunk (29 cycles, 30 count) apart from the one-chunk ones (tps, nps)
+__device__ __forceinline__ void q3_prof_ins_end(Q3Prof& F, const Q3InsProf& I, int np) {
+#ifdef LQRO_QHULL_PROFILE
+  F.prev1 = np <= 64;
+  if (np > 64) { F.tph[29] += F.tq - I.tins; F.tph[30] += 1; }
+  else {
+    for (int k = 0; k < 21; k++) F.tps[k] += F.tph[k] - I.snap[k];
+    F.nps += 1;
+  }
+#endif
+}
+
+// q3_body, wave 1: a speculation begins (t0, ts: for the hooks after it)
+template <class LT>
+__device__ __forceinline__ void q3_prof_spec_begin(LT& L, Q3P& P, Q3Cy& t0, Q3Rt& ts, int lane) {
+  q3_cy_now(t0);
+#ifdef LQRO_QHULL_PROFILE
+  P.tq = t0.t;
+  P.t[14] += t0.t - L.pub_t;   // publication -> speculation start
+  if (P.tq2) P.t[15] += t0.t - P.tq2;   // (this wave's clock) its last speculation's end -> this start
+  if (lane == 0) L.start_r = __builtin_amdgcn_s_memrealtime();
+#endif
+  q3_rt_now(ts);
+}
+// it is over, before its results are released
+template <class LT>
+__device__ __forceinline__ void q3_prof_spec_done(LT& L, const Q3Rt& ts, int lane) {
+#ifdef LQRO_QHULL_LONGPROF
+  if (lane == 0) {
+    const unsigned long long te_ = __builtin_amdgcn_s_memrealtime();
+    L.hprof[3] += 1; L.hprof[4] += ts.t - Q3_PROF_LDS(L.lp_pubr); L.hprof[5] += te_ - ts.t;
+    L.lp_doner = te_;
+  }
+#endif
+#ifdef LQRO_QHULL_PROFILE
+  if (lane == 0) L.done_t = __builtin_amdgcn_s_memtime();
+#endif
+}
+// and after the release and the prescan
+template <class LT>
+__device__ __forceinline__ void q3_prof_spec_end(LT& L, Q3P& P, const Q3Cy& t0, int lane) {
+#ifdef LQRO_QHULL_PROFILE
+  if (lane == 0) { L.done_t2 = __builtin_amdgcn_s_memtime(); L.done_r = __builtin_amdgcn_s_memrealtime(); }
+  P.tq2 = __builtin_amdgcn_s_memtime();
+  P.t[0] += __builtin_amdgcn_s_memtime() - t0.t;
+  P.t[7] += 1;
+#endif
+}
+// wave 1 located a posted chunk (since t0)
+__device__ __forceinline__ void q3_prof_w1_helped(Q3P& P, const Q3Cy& t0) {
+#ifdef LQRO_QHULL_PROFILE
+  P.t[6] += __builtin_amdgcn_s_memtime() - t0.t;
+  P.t[8] += 1;
 #endif
 }
 
