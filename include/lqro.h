@@ -509,6 +509,109 @@ int lqro_get_hull_failures(lqro_ctx* ctx, int64_t* pairs, int64_t capacity, int6
  * the context's stream: [0]=pair sweep+GJK, [1]=hull, [2]=LP, [3]=whole step. */
 int lqro_get_timings(lqro_ctx* ctx, float* ms4);
 
+/* ---- clearance: did the swarm stay clear of anything? -------------------
+ * An opt-in measurement, on the device, of each own row agent i against
+ * every column: the agents c != i, then the obstacle columns n_agents + o of
+ * lqro_set_obstacles[_ex] as the step reads them.  The reference has no
+ * counterpart (its loop never asks); the body model is the method's own,
+ * createSpheres over the summed radii (LQRO:735-750): column c's ellipsoid
+ * has the semi-axes a_c = xy_radius + rxy_c, b_c = z_radius + rz_c, with
+ * (rxy_c, rz_c) the configuration's radii for an agent column (a_c is the
+ * reference's 2*XYRADIUS bit for bit) and the obstacle's own for an obstacle.
+ * The host forms wxy_c = 1.0 / (a_c a_c), wz_c = 1.0 / (b_c b_c) once; then,
+ * with p = x[.][0..2], all fp64 and every operation rounded once:
+ *   dx = p_i.x - p_c.x (dy, dz likewise); q = dx dx + dy dy; d2 = q + dz dz;
+ *   s2 = q wxy_c + (dz dz) wz_c;  the pair is a HIT when s2 < 1.0, strictly.
+ * Self is skipped by index, never by distance (two agents at one point are a
+ * hit with s2 == 0).  lqro_set_neighbors does not apply: every column counts.
+ * Columns are numbered 0 .. n_agents + M - 1.  With lqro_set_fence active a
+ * row's fence margin is the minimum over the emitted faces of
+ *   lower face, axis a:  p[a] - (lo[a] + m[a])      (face index 2 a)
+ *   upper face, axis a:  (hi[a] - m[a]) - p[a]      (face index 2 a + 1)
+ * m = (xy_radius, xy_radius, z_radius): the fence planes' own expression
+ * without the division by tau, the sign turned; the lowest face index wins a
+ * tie; the row is OUT when the margin is < 0 (on a face, 0.0, is not out).
+ * Inputs must be finite.  The result is deterministic: minima are taken over
+ * (value, index) keys, counts are integers, no floating-point atomics; it
+ * does not depend on schedule or wave count, and a numpy restatement
+ * (tests/clearance_ref.py) matches it bit for bit. */
+typedef struct lqro_clearance_row {
+  double s2_min;       /* smallest s2 over the columns (+inf: no columns)         */
+  double d2_min;       /* smallest d2 over the columns (+inf: no columns)         */
+  double fence_min;    /* the fence margin; +inf without a fence                  */
+  int32_t j_s2;        /* column of s2_min: the smallest on equal values; -1: none */
+  int32_t j_d2;        /* column of d2_min, same tie rule                         */
+  int32_t n_hit;       /* hit columns of this row: the true count, even past six  */
+  int32_t fence_face;  /* the face 2 a + side that attains fence_min; -1: no fence */
+  int32_t hit[6];      /* the first six hit columns, ascending, -1 padded         */
+} lqro_clearance_row;
+
+/* Over a context's own rows.  Ties: the smallest (value, i, j) wins.  n_hit
+ * counts ordered pairs over the own rows: a context that owns every row
+ * counts a touching agent pair twice, an agent-obstacle pair once.  A
+ * minimum that is +inf (fence_min without a fence) has indices -1. */
+typedef struct lqro_clearance_total {
+  double s2_min, d2_min, fence_min;
+  int32_t s2_i, s2_j;          /* the pair of s2_min                              */
+  int32_t d2_i, d2_j;          /* the pair of d2_min                              */
+  int32_t fence_i, fence_face; /* the row and face of fence_min                   */
+  int64_t n_hit;               /* sum of the rows' n_hit                          */
+  int64_t n_rows_hit;          /* rows with n_hit > 0                             */
+  int64_t n_fence_out;         /* rows with fence_min < 0                         */
+  int64_t n_measured;          /* measurements folded in (1 for a last total)     */
+} lqro_clearance_total;
+#ifdef __cplusplus
+static_assert(sizeof(lqro_clearance_row) == 64, "lqro_clearance_row is 64 bytes");
+static_assert(sizeof(lqro_clearance_total) == 80, "lqro_clearance_total is 80 bytes");
+#endif
+
+/* The context keeps two totals on the device: LAST, the last measurement
+ * (n_measured = 1), and SINCE RESET, minima of minima and sums of counts over
+ * every measurement since the last reset, its (i, j) those of the earliest
+ * measurement that attains the minimum.  Explicit calls and the per-step
+ * monitor both update them.  A row shard measures its own rows against all
+ * columns; the caller merges the ranks' totals (min and sum with the tie
+ * rules above: lqro.py merge_clearance; lqro::ShardedSimulator does not).
+ * All calls: LQRO_E_ARG for a configuration whose xy_radius or z_radius is
+ * not positive and finite; LQRO_E_STATE from lqro_clearance[_device] and
+ * lqro_set_monitor while a lqro_step_device_begin is pending.  The buffers
+ * are allocated by the first call that needs them, after the last step, and
+ * never inside a step; lqro_set_obstacles* and lqro_set_fence keep the
+ * monitor setting and the since-reset total. */
+
+/* Measures the N x X host array x (the estimates or a caller's xTrue): copies
+ * in, measures, waits, copies out.  rows: the context's own rows in row
+ * order (NULL: not wanted); total: this measurement's (NULL: not wanted). */
+int lqro_clearance(lqro_ctx* ctx, const double* x /* N*X, host */, lqro_clearance_row* rows /* nrows, may be NULL */,
+                   lqro_clearance_total* total /* may be NULL */);
+/* The same on a device array, asynchronous on the caller's stream (NULL: the
+ * null stream, as in lqro_step_device), ordered behind the context's last
+ * step and last measurement by event waits on that stream; once the buffers
+ * exist it never waits on the host.  d_rows NULL: the context's own row
+ * buffer; else the caller's nrows records, which lqro_get_monitor_rows /
+ * _pairs then read: keep them alive until the next measurement. */
+int lqro_clearance_device(lqro_ctx* ctx, const double* d_x, lqro_clearance_row* d_rows, void* stream);
+/* on = 1: every lqro_step, lqro_step_device and lqro_step_device_begin
+ * measures its own columns (the step's x and the obstacle states it reads) at
+ * the head of the step, on the step's stream.  Nothing in the step reads the
+ * result: newV, records, statistics and the carried normal are bit-identical
+ * to a context without the monitor.  on = 0 (the default): no launch, no
+ * buffer use.  Another value: LQRO_E_ARG. */
+int lqro_set_monitor(lqro_ctx* ctx, int32_t on);
+/* Waits for the last step or measurement (like lqro_get_stats), then copies
+ * the two totals (either may be NULL); reset != 0 clears the since-reset
+ * total after reading it.  A context that never measured: both cleared
+ * (minima +inf, indices -1, counts 0). */
+int lqro_get_monitor(lqro_ctx* ctx, lqro_clearance_total* last, lqro_clearance_total* since_reset, int32_t reset);
+/* The last measurement's rows (capacity < the own rows: LQRO_E_ARG; no
+ * measurement yet: *n_out = 0). */
+int lqro_get_monitor_rows(lqro_ctx* ctx, lqro_clearance_row* rows, int64_t capacity, int64_t* n_out);
+/* The last measurement's hit pairs (i, column) in (i, column) order, two
+ * words a pair, assembled on the host from the rows' hit[]: at most six from
+ * one row, so compare *n_out, the number written (at most capacity), with
+ * the total's n_hit. */
+int lqro_get_monitor_pairs(lqro_ctx* ctx, int64_t* pairs /* 2 per pair */, int64_t capacity, int64_t* n_out);
+
 /* ---- the per-agent step after the pair loop ------
  * Replaces the agent loop LQRO:1437-1446: vGoal = newV; u = findU()
  * (riccatiControllerSteady, LQRO:594-617); propagateU (propagate,

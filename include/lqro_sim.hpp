@@ -184,6 +184,27 @@ class Simulator {
   // default) is the reference's LP.
   void setHardPlanes(int32_t level) { check(lqro_set_hard_planes(ctx_, level), "lqro_set_hard_planes"); }
 
+  // Clearance (lqro_clearance): how clear every agent's current estimate
+  // Quadrotor::x is of every other agent and obstacle, and of the fence;
+  // rows, when given, receives one record per agent.  Returns the total.
+  lqro_clearance_total clearance(std::vector<lqro_clearance_row>* rows = nullptr) {
+    for (size_t i = 0; i < q_.size(); ++i)
+      for (int c = 0; c < kX; ++c) xs_[i * kX + c] = q_[i].x[c];
+    if (rows) rows->resize(q_.size());
+    lqro_clearance_total t;
+    check(lqro_clearance(ctx_, xs_.data(), rows ? rows->data() : nullptr, &t), "lqro_clearance");
+    return t;
+  }
+  // The per-step monitor (lqro_set_monitor): with on, every step() measures
+  // the x it reads, on the device; monitor() returns the last step's total
+  // and, in *since_reset when given, the one accumulated since the last reset.
+  void setMonitor(bool on) { check(lqro_set_monitor(ctx_, on ? 1 : 0), "lqro_set_monitor"); }
+  lqro_clearance_total monitor(lqro_clearance_total* since_reset = nullptr, bool reset = false) {
+    lqro_clearance_total last;
+    check(lqro_get_monitor(ctx_, &last, since_reset, reset ? 1 : 0), "lqro_get_monitor");
+    return last;
+  }
+
   // The pair loop LQRO:1393-1436 on the GPU: every Quadrotor::newV.
   // LQRO_E_HULL (a pair without its half-plane) and LQRO_E_QHMERGE (a pair
   // whose winning facet qconvex's pre-merge may join: its half-plane is not

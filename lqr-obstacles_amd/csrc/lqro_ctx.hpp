@@ -111,6 +111,16 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   double *d_So, *d_Ro;            // n_ocls x (NP x 3), then n_ocls x 4 (semi-axes, max |u_p|: pa.osc);
                                   // n_ocls x n_agents x H (the row of agent 0 with shared gains)
   int lds_attr;                   // the dynamic LDS size the k_pair instantiations are set to
+  // clearance (lqro_clearance[_device], lqro_set_monitor): allocated by the
+  // first call that needs them, never in a step
+  int monitor;                    // lqro_set_monitor: every step measures its own columns
+  int measured;                   // a measurement was enqueued (cev recorded)
+  hipEvent_t cev;                 // the last measurement's end, on whichever stream it ran
+  double* d_clpack;               // 5 x (n_agents + nobs): px py pz wxy wz
+  double* d_clow;                 // nobs x 2: the obstacle columns' wxy, wz (lqro_set_obstacles)
+  lqro_clearance_row* d_clrows;   // nrows: the context's own row buffer
+  const lqro_clearance_row* cl_last;   // the last measurement's rows: d_clrows or the caller's
+  lqro_clearance_total* d_cltot;  // [0] last, [1] since reset
   lqro::PairArgs pa;
   lqro::DevPool mem;              // owns every d_* buffer above that is not the caller's
 };
@@ -123,6 +133,10 @@ void sphere_axes(int np, double axy, double az, double* out);   // (lqro_synth.c
 // enqueued on (the caller's for lqro_step_device): wait on that, not on
 // c->stream; a context that never stepped has nothing to wait for
 static inline hipError_t wait_last_step(lqro_ctx* c) {
+  if (c->measured) {   // ... and the last clearance measurement, wherever it was enqueued
+    const hipError_t e = hipEventSynchronize(c->cev);
+    if (e != hipSuccess) return e;
+  }
   if (!c->stepped) return hipStreamSynchronize(c->stream);
   return hipEventSynchronize(c->ev[3]);
 }

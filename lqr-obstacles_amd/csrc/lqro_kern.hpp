@@ -68,7 +68,27 @@ struct FenceArgs {
   float* out;
 };
 
+// The clearance measurement (lqro_clearance[_device], lqro_set_monitor;
+// lqro_kern_clear.hip): own rows against every column, lqro.h's contract.
+// pack: the columns as a structure of arrays, px py pz wxy wz, ncols each.
+struct ClearArgs {
+  int n_agents, nobs, X;
+  int nrows, row_begin, row_stride;
+  const double* x;      // n_agents x X: the agents' states
+  const double* obs;    // nobs x X: the obstacles' states as the step reads them
+  const double* ow;     // nobs x 2: the obstacles' wxy, wz
+  double wxy, wz;       // the agent columns' weights
+  double* pack;         // 5 x (n_agents + nobs)
+  int faces;            // the fence: bit 2 a + side (0: no fence)
+  double lo[3], hi[3], m[3];
+  lqro_clearance_row* rows;     // nrows records, the own rows in row order
+  lqro_clearance_total* tot;    // [0] last, [1] since reset
+};
+
 namespace lqro {
+// k_clear_pack, k_clear, k_clear_total: one measurement (ev: four timing
+// events recorded around the three kernels, scripts/clearance_bench.py; else null)
+void launch_clear(hipStream_t s, const ClearArgs& A, hipEvent_t* ev = nullptr);
 struct HullArgs;
 struct ObsSlots;   // (lqro_hull_job.hpp)
 // k_tables: one workgroup per agent with gains of its own (n_gains: 1 or N)

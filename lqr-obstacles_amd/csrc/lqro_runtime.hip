@@ -58,6 +58,7 @@ void lqro_destroy(lqro_ctx* c) {
     if (c->xev[k]) (void)hipEventDestroy(c->xev[k]);
     if (c->iev[k]) (void)hipEventDestroy(c->iev[k]);
   }
+  if (c->cev) (void)hipEventDestroy(c->cev);
   if (c->h_feedback) (void)hipHostFree(c->h_feedback);
   if (c->side) (void)hipStreamDestroy(c->side);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -143,6 +144,7 @@ static int ctx_alloc(lqro_ctx* c) {
   for (int k = 0; k < 5; ++k) HIPCHK(hipEventCreate(&c->ev[k]));
   HIPCHK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
   for (int k = 0; k < 2; ++k) HIPCHK(hipEventCreateWithFlags(&c->xev[k], hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&c->cev, hipEventDisableTiming));
   // one line per buffer: member, elements[, the byte every element starts as]
 #define BUF(member, ...) HIPCHK((hipError_t)c->mem.get(c->member, __VA_ARGS__))
   BUF(d_S, NP * 3);
@@ -491,17 +493,29 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, const double*
   // every new buffer first: a failed call leaves the context as it was
   const int npr = (int)N - 1 + M;
   double *cols = nullptr, *copy = nullptr, *dSo = nullptr, *dRo = nullptr, *dresp = nullptr;
+  double *clow = nullptr, *clpack = nullptr;   // clearance: the columns' weights; the pack buffer once it exists
   int* dcls = nullptr;
   SlotBufs sb{};
   int rc = LQRO_OK;
   if (M > 0 && (c->mem.get(cols, (N + M) * X) || c->mem.get(dresp, (size_t)M))) rc = LQRO_E_NOMEM;
   if (!rc && M > 0 && own && c->mem.get(copy, (size_t)M * X)) rc = LQRO_E_NOMEM;
+  if (!rc && M > 0 && c->mem.get(clow, 2 * (size_t)M)) rc = LQRO_E_NOMEM;
+  if (!rc && c->d_clpack && M != c->nobs && c->mem.get(clpack, 5 * (N + M))) rc = LQRO_E_NOMEM;
   if (!rc && K > 0 && (c->mem.get(dSo, (size_t)K * (3 * NP + 4)) || c->mem.get(dRo, (size_t)K * N * H) ||
                        c->mem.get(dcls, (size_t)M)))
     rc = LQRO_E_NOMEM;
   if (!rc && npr != c->npr) rc = slots_alloc(c, npr, sb);
   if (!rc && copy && hipMemcpy(copy, states, sizeof(double) * M * X, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
   if (!rc && M > 0 && hipMemcpy(dresp, resp, sizeof(double) * M, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  if (!rc && M > 0) {   // wxy = 1 / a^2, wz = 1 / b^2 over the summed radii, once, in fp64
+    std::vector<double> w(2 * (size_t)M);
+    for (int o = 0; o < M; ++o) {
+      const double a = g.xy_radius + oxy[o], b = g.z_radius + oz[o];
+      w[2 * o] = 1.0 / (a * a);
+      w[2 * o + 1] = 1.0 / (b * b);
+    }
+    if (hipMemcpy(clow, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  }
   if (!rc && K > 0 &&
       (hipMemcpy(dSo, So.data(), sizeof(double) * So.size(), hipMemcpyHostToDevice) != hipSuccess ||
        hipMemcpy(dSo + So.size(), osc.data(), sizeof(double) * osc.size(), hipMemcpyHostToDevice) != hipSuccess ||
@@ -510,7 +524,7 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, const double*
   if (!rc && !pair_set_lds(lds_bytes)) rc = LQRO_E_HIP;
   if (rc) {
     c->mem.release(cols); c->mem.release(copy); c->mem.release(dSo); c->mem.release(dRo);
-    c->mem.release(dresp); c->mem.release(dcls);
+    c->mem.release(dresp); c->mem.release(dcls); c->mem.release(clow); c->mem.release(clpack);
     slots_release(c, sb);
     (void)pair_set_lds(c->lds_bytes);
     return rc;
@@ -528,6 +542,9 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, const double*
   }
   c->mem.release(c->d_cols); c->mem.release(c->d_obsown); c->mem.release(c->d_So); c->mem.release(c->d_Ro);
   c->mem.release(c->d_oresp); c->mem.release(c->d_ocls);
+  c->mem.release(c->d_clow);
+  c->d_clow = clow;
+  if (clpack) { c->mem.release(c->d_clpack); c->d_clpack = clpack; }
   c->d_cols = cols; c->d_obsown = copy; c->d_So = dSo; c->d_Ro = dRo; c->d_oresp = dresp; c->d_ocls = dcls;
   c->d_obs = M > 0 ? (own ? copy : states) : nullptr;
   c->nobs = M;
@@ -769,6 +786,32 @@ static HullArgs handed_over(const lqro_ctx* c, HullArgs H) {
   return H;
 }
 
+// One clearance measurement on s: the agents of d_x and the context's
+// obstacles against the own rows, into `rows`; the totals folded.  The caller
+// has ordered s behind the last step; the buffers exist.
+static int enqueue_clear(lqro_ctx* c, const double* d_x, lqro_clearance_row* rows, hipStream_t s,
+                         hipEvent_t* ev = nullptr) {
+  const lqro_config& g = c->cfg;
+  if (c->measured) HIPCHK(hipStreamWaitEvent(s, c->cev, 0));   // (the last measurement may be on another stream)
+  ClearArgs A{};
+  A.n_agents = g.n_agents; A.nobs = c->nobs; A.X = g.x_dim;
+  A.nrows = c->nrows; A.row_begin = c->rb; A.row_stride = c->rs;
+  A.x = d_x; A.obs = c->d_obs; A.ow = c->d_clow;
+  const double a = g.xy_radius + g.xy_radius, b = g.z_radius + g.z_radius;   // createSpheres' 2 XYRADIUS, 2 ZRADIUS
+  A.wxy = 1.0 / (a * a); A.wz = 1.0 / (b * b);
+  A.pack = c->d_clpack;
+  A.faces = c->nfence > 0 ? c->fence_faces : 0;
+  for (int q = 0; q < 3; ++q) {
+    A.lo[q] = c->fence_lo[q]; A.hi[q] = c->fence_hi[q]; A.m[q] = q < 2 ? g.xy_radius : g.z_radius;
+  }
+  A.rows = rows; A.tot = c->d_cltot;
+  LAUNCH(launch_clear(s, A, ev));
+  HIPCHK(hipEventRecord(c->cev, s));
+  c->measured = 1;
+  c->cl_last = rows;
+  return LQRO_OK;
+}
+
 // The step's first launches on the caller's stream: behind the last step, the
 // counters and queues reset, the neighbour lists, the hot list.
 static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, const double* d_x, hipStream_t s) {
@@ -802,6 +845,9 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
     F.x = P.x; F.out = c->d_fence;
     LAUNCH(launch_fence(s, F));
   }
+  // the monitor: this step's own columns, behind k_cols and k_fence; nothing in the step reads it
+  if (c->monitor)
+    if (int rc = enqueue_clear(c, d_x, c->d_clrows, s)) return rc;
   if (plan.hot) {
     const PrioArgs Q = prio_args(c, plan, P);
     if (plan.split) {
@@ -1079,6 +1125,134 @@ int lqro_step(lqro_ctx* c, const double* x, const double* vgoal, double* newv) {
   // a pair whose winner qconvex may have merged (Qhull's pre-merge is not
   // restated): never a silent difference from the reference (LQRO:925-967)
   if (st[LQRO_ST_MWIN]) return LQRO_E_QHMERGE;
+  return LQRO_OK;
+}
+
+// ---- clearance -----------------------------------------------------------
+static const lqro_clearance_total kClearNone = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val(),
+                                                -1, -1, -1, -1, -1, -1, 0, 0, 0, 0};
+
+static bool clear_radii_ok(const lqro_ctx* c) {
+  const double a = c->cfg.xy_radius, b = c->cfg.z_radius;
+  return a > 0 && b > 0 && std::isfinite(a) && std::isfinite(b);
+}
+
+// the measurement's buffers, once; the caller has waited for the last step
+static int clear_reserve(lqro_ctx* c) {
+  if (c->d_cltot) return LQRO_OK;
+  double* pack = nullptr;
+  lqro_clearance_row* rows = nullptr;
+  lqro_clearance_total* tot = nullptr;
+  if (c->mem.get(pack, 5 * ((size_t)c->cfg.n_agents + c->nobs)) || c->mem.get(rows, (size_t)c->nrows) ||
+      c->mem.get(tot, 2)) {
+    c->mem.release(pack); c->mem.release(rows);
+    return LQRO_E_NOMEM;
+  }
+  const lqro_clearance_total t[2] = {kClearNone, kClearNone};
+  if (hipMemcpy(tot, t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) {
+    c->mem.release(pack); c->mem.release(rows); c->mem.release(tot);
+    return LQRO_E_HIP;
+  }
+  c->d_clpack = pack; c->d_clrows = rows; c->d_cltot = tot;
+  return LQRO_OK;
+}
+
+int lqro_set_monitor(lqro_ctx* c, int32_t on) {
+  if (!c || (on != 0 && on != 1)) return LQRO_E_ARG;
+  if (on && !clear_radii_ok(c)) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;   // the pending half-step measured, or did not, as it was set
+  if (int rc = ctx_enter(c, false)) return rc;
+  if (on)
+    if (int rc = clear_reserve(c)) return rc;
+  c->monitor = on;
+  return LQRO_OK;
+}
+
+int lqro_clearance_device(lqro_ctx* c, const double* d_x, lqro_clearance_row* d_rows, void* stream) {
+  if (!c || !d_x || !clear_radii_ok(c)) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  if (!c->d_cltot) {   // the first call that needs the buffers: after the last step; later calls never wait
+    HIPCHK(wait_last_step(c));
+    if (int rc = clear_reserve(c)) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (c->stepped) HIPCHK(hipStreamWaitEvent(s, c->ev[3], 0));   // behind the context's last step
+  return enqueue_clear(c, d_x, d_rows ? d_rows : c->d_clrows, s);
+}
+
+int lqro_clearance(lqro_ctx* c, const double* x, lqro_clearance_row* rows, lqro_clearance_total* total) {
+  if (!c || !x || !clear_radii_ok(c)) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  if (int rc = clear_reserve(c)) return rc;
+  const lqro_config& g = c->cfg;
+  HIPCHK(hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)g.n_agents * g.x_dim, hipMemcpyHostToDevice, c->stream));
+  if (int rc = enqueue_clear(c, c->d_x, c->d_clrows, c->stream)) return rc;
+  if (rows)
+    HIPCHK(hipMemcpyAsync(rows, c->d_clrows, sizeof(lqro_clearance_row) * (size_t)c->nrows, hipMemcpyDeviceToHost,
+                          c->stream));
+  if (total) HIPCHK(hipMemcpyAsync(total, c->d_cltot, sizeof *total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return LQRO_OK;
+}
+
+// scripts/clearance_bench.py: one measurement of the device array d_x on the
+// context's stream, a measurement like any other, with the three kernels'
+// own times from HIP events (ms: k_clear_pack, k_clear, k_clear_total).
+// Synchronous; declared where it is used, like the lqro_debug_* hooks.
+int lqro_debug_clearance_times(lqro_ctx* c, const double* d_x, float* ms3) {
+  if (!c || !d_x || !ms3 || !clear_radii_ok(c)) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  if (int rc = clear_reserve(c)) return rc;
+  hipEvent_t ev[4] = {};
+  int rc = LQRO_OK;
+  for (int k = 0; k < 4 && rc == LQRO_OK; ++k)
+    if (hipEventCreate(&ev[k]) != hipSuccess) rc = LQRO_E_HIP;
+  if (rc == LQRO_OK) rc = enqueue_clear(c, d_x, c->d_clrows, c->stream, ev);
+  if (rc == LQRO_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = LQRO_E_HIP;
+  for (int k = 0; k < 3 && rc == LQRO_OK; ++k)
+    if (hipEventElapsedTime(&ms3[k], ev[k], ev[k + 1]) != hipSuccess) rc = LQRO_E_HIP;
+  for (int k = 0; k < 4; ++k)
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+  return rc;
+}
+
+int lqro_get_monitor(lqro_ctx* c, lqro_clearance_total* last, lqro_clearance_total* since_reset, int32_t reset) {
+  if (!c) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;   // (pending: the half-step's measurement is not ordered yet)
+  lqro_clearance_total t[2] = {kClearNone, kClearNone};
+  if (c->d_cltot) HIPCHK(hipMemcpy(t, c->d_cltot, sizeof t, hipMemcpyDeviceToHost));
+  if (last) *last = t[0];
+  if (since_reset) *since_reset = t[1];
+  if (reset && c->d_cltot) HIPCHK(hipMemcpy(c->d_cltot + 1, &kClearNone, sizeof kClearNone, hipMemcpyHostToDevice));
+  return LQRO_OK;
+}
+
+int lqro_get_monitor_rows(lqro_ctx* c, lqro_clearance_row* rows, int64_t cap, int64_t* n_out) {
+  if (!c || !n_out || (cap > 0 && !rows)) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  *n_out = 0;
+  if (!c->cl_last) return LQRO_OK;
+  if (cap < c->nrows) return LQRO_E_ARG;
+  HIPCHK(hipMemcpy(rows, c->cl_last, sizeof(lqro_clearance_row) * (size_t)c->nrows, hipMemcpyDeviceToHost));
+  *n_out = c->nrows;
+  return LQRO_OK;
+}
+
+int lqro_get_monitor_pairs(lqro_ctx* c, int64_t* pairs, int64_t cap, int64_t* n_out) {
+  if (!c || !n_out || (cap > 0 && !pairs)) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  *n_out = 0;
+  if (!c->cl_last) return LQRO_OK;
+  std::vector<lqro_clearance_row> h((size_t)c->nrows);
+  HIPCHK(hipMemcpy(h.data(), c->cl_last, sizeof(lqro_clearance_row) * h.size(), hipMemcpyDeviceToHost));
+  int64_t n = 0;
+  for (int r = 0; r < c->nrows && n < cap; ++r)
+    for (int q = 0; q < 6 && h[r].hit[q] >= 0 && n < cap; ++q, ++n) {
+      pairs[2 * n] = c->rb + (int64_t)r * c->rs;
+      pairs[2 * n + 1] = h[r].hit[q];
+    }
+  *n_out = n;
   return LQRO_OK;
 }
 

@@ -74,6 +74,52 @@ RECORD_DTYPE = np.dtype([
 ])
 assert RECORD_DTYPE.itemsize == C.sizeof(PairRecord) == 168
 
+class ClearanceRow(C.Structure):
+    """lqro_clearance_row: one own row's separation from every column."""
+    _fields_ = [("s2_min", C.c_double), ("d2_min", C.c_double), ("fence_min", C.c_double),
+                ("j_s2", C.c_int32), ("j_d2", C.c_int32), ("n_hit", C.c_int32), ("fence_face", C.c_int32),
+                ("hit", C.c_int32 * 6)]
+
+
+class ClearanceTotal(C.Structure):
+    """lqro_clearance_total: the minima and counts over a context's own rows."""
+    _fields_ = [("s2_min", C.c_double), ("d2_min", C.c_double), ("fence_min", C.c_double),
+                ("s2_i", C.c_int32), ("s2_j", C.c_int32), ("d2_i", C.c_int32), ("d2_j", C.c_int32),
+                ("fence_i", C.c_int32), ("fence_face", C.c_int32),
+                ("n_hit", C.c_int64), ("n_rows_hit", C.c_int64), ("n_fence_out", C.c_int64),
+                ("n_measured", C.c_int64)]
+
+
+CLEARANCE_ROW_DTYPE = np.dtype([("s2_min", "<f8"), ("d2_min", "<f8"), ("fence_min", "<f8"), ("j_s2", "<i4"),
+                                ("j_d2", "<i4"), ("n_hit", "<i4"), ("fence_face", "<i4"), ("hit", "<i4", (6,))])
+assert CLEARANCE_ROW_DTYPE.itemsize == C.sizeof(ClearanceRow) == 64 and C.sizeof(ClearanceTotal) == 80
+CLEARANCE_TOTAL_FIELDS = tuple(n for n, _ in ClearanceTotal._fields_)
+
+
+def _total_dict(t: ClearanceTotal) -> dict:
+    return {n: getattr(t, n) for n in CLEARANCE_TOTAL_FIELDS}
+
+
+def merge_clearance(totals) -> dict:
+    """The ranks' totals of one measurement (or of the same measurements since
+    a reset) as one: each minimum is the smallest (value, i, j) over the
+    shards (a +inf minimum has indices -1), the counts are summed, n_measured
+    is the shards' common count (its largest).  Row shards partition the rows,
+    so the merge of a block or cyclic split equals the single context's
+    total."""
+    totals = list(totals)
+    out = dict(s2_min=np.inf, s2_i=-1, s2_j=-1, d2_min=np.inf, d2_i=-1, d2_j=-1, fence_min=np.inf, fence_i=-1,
+               fence_face=-1, n_hit=0, n_rows_hit=0, n_fence_out=0, n_measured=0)
+    for v, a, b in (("s2_min", "s2_i", "s2_j"), ("d2_min", "d2_i", "d2_j"), ("fence_min", "fence_i", "fence_face")):
+        keys = [(float(t[v]), int(t[a]), int(t[b])) for t in totals if float(t[v]) < np.inf]
+        if keys:
+            out[v], out[a], out[b] = min(keys)
+    for k in ("n_hit", "n_rows_hit", "n_fence_out"):
+        out[k] = sum(int(t[k]) for t in totals)
+    out["n_measured"] = max([int(t["n_measured"]) for t in totals], default=0)
+    return out
+
+
 # every symbol include/lqro.h declares
 EXPORTS = (
     "lqro_config_default", "lqro_model_default", "lqro_synthesize_gains", "lqro_sphere",
@@ -89,6 +135,8 @@ EXPORTS = (
     "lqro_set_obstacles", "lqro_set_obstacles_device",
     "lqro_set_obstacles_ex", "lqro_set_obstacles_ex_device",
     "lqro_set_hard_planes", "lqro_calculate_new_v_hard",
+    "lqro_clearance", "lqro_clearance_device", "lqro_set_monitor", "lqro_get_monitor",
+    "lqro_get_monitor_rows", "lqro_get_monitor_pairs",
 )
 # lqro_set_hard_planes' levels: the planes linearProgram4 does not relax
 LQRO_HARD_NONE, LQRO_HARD_FENCE, LQRO_HARD_HEAD, LQRO_HARD_OBSTACLES = 0, 1, 2, 3
@@ -154,6 +202,13 @@ def lib() -> C.CDLL:
         if hasattr(L, "lqro_set_hard_planes"):   # (older libraries in A/B runs lack them)
             L.lqro_set_hard_planes.argtypes = [vp, i32]
             L.lqro_calculate_new_v_hard.argtypes = [vp, vp, vp, i32, vp, dbl, vp, i32]
+        if hasattr(L, "lqro_clearance"):   # (older libraries in A/B runs lack them)
+            L.lqro_clearance.argtypes = [vp, vp, vp, C.POINTER(ClearanceTotal)]
+            L.lqro_clearance_device.argtypes = [vp, vp, vp, vp]
+            L.lqro_set_monitor.argtypes = [vp, i32]
+            L.lqro_get_monitor.argtypes = [vp, C.POINTER(ClearanceTotal), C.POINTER(ClearanceTotal), i32]
+            L.lqro_get_monitor_rows.argtypes = [vp, vp, i64, C.POINTER(i64)]
+            L.lqro_get_monitor_pairs.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.lqro_set_carry_normal.argtypes = [vp, vp]
         L.lqro_get_carry_normal.argtypes = [vp, vp]
         _lib = L
@@ -402,6 +457,58 @@ class Context:
         infeasible among themselves guarantee nothing.  The level stays when
         fence, user planes or obstacles are set or cleared later."""
         _check(lib().lqro_set_hard_planes(self._h, int(level)), "lqro_set_hard_planes")
+
+    def clearance(self, x):
+        """How clear the own rows of the (n_agents, x_dim) host array x are of
+        every column (lqro_clearance: the agents j != i, then the obstacles as
+        the step reads them; lqro.h states the formulas): (rows, total) — a
+        CLEARANCE_ROW_DTYPE array in own-row order and the total as a dict.
+        Also becomes the context's last total and folds into its since-reset
+        one (monitor())."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.cfg.n_agents, self.cfg.x_dim):
+            raise LqroError(f"clearance: x has shape {x.shape}, expected {(self.cfg.n_agents, self.cfg.x_dim)}")
+        rows = np.zeros(len(self.row_ids), dtype=CLEARANCE_ROW_DTYPE)
+        t = ClearanceTotal()
+        _check(lib().lqro_clearance(self._h, _p(x), _p(rows), C.byref(t)), "lqro_clearance")
+        return rows, _total_dict(t)
+
+    def clearance_device(self, ptr: int, rows_ptr: int = 0, stream: int = 0):
+        """The same on a device array (e.g. x_true.data_ptr()), enqueued on
+        `stream` behind the context's last step, without a host wait
+        (lqro_clearance_device).  rows_ptr = 0: the context's own row buffer;
+        monitor() / monitor_rows() read the result."""
+        _check(lib().lqro_clearance_device(self._h, C.c_void_p(ptr or None), C.c_void_p(rows_ptr or None),
+                                           C.c_void_p(stream or None)), "lqro_clearance_device")
+
+    def set_monitor(self, on):
+        """on: every step measures its own columns at its head, on the step's
+        stream, and accumulates on the device (lqro_set_monitor); the step's
+        results do not change.  Off: no launch."""
+        _check(lib().lqro_set_monitor(self._h, int(on)), "lqro_set_monitor")
+
+    def monitor(self, reset: bool = False):
+        """(last, since_reset) totals as dicts, after waiting for the last
+        step or measurement (lqro_get_monitor); reset clears the since-reset
+        total after reading it."""
+        a, b = ClearanceTotal(), ClearanceTotal()
+        _check(lib().lqro_get_monitor(self._h, C.byref(a), C.byref(b), int(bool(reset))), "lqro_get_monitor")
+        return _total_dict(a), _total_dict(b)
+
+    def monitor_rows(self) -> np.ndarray:
+        """The last measurement's rows (empty before the first)."""
+        rows = np.zeros(len(self.row_ids), dtype=CLEARANCE_ROW_DTYPE)
+        n = C.c_int64()
+        _check(lib().lqro_get_monitor_rows(self._h, _p(rows), len(rows), C.byref(n)), "lqro_get_monitor_rows")
+        return rows[:n.value]
+
+    def monitor_pairs(self) -> np.ndarray:
+        """The last measurement's hit pairs (i, column) in (i, column) order,
+        at most six a row: compare len() with the total's n_hit."""
+        out = np.zeros((6 * len(self.row_ids), 2), np.int64)
+        n = C.c_int64()
+        _check(lib().lqro_get_monitor_pairs(self._h, _p(out), len(out), C.byref(n)), "lqro_get_monitor_pairs")
+        return out[:n.value]
 
     def set_gains(self, A, B, L, E, per_agent: bool = False):
         A, B, L, E = (np.ascontiguousarray(v, dtype=np.float64) for v in (A, B, L, E))
@@ -795,6 +902,10 @@ class Simulator:
         (Context.set_hard_planes)."""
         self.ctx.set_hard_planes(level)
 
+    def clearance(self):
+        """Context.clearance on the agents' current estimates q.x."""
+        return self.ctx.clearance(np.stack([q.x for q in self.qlist]))
+
     def step(self):
         x = np.stack([q.x for q in self.qlist])
         vg = np.stack([q.vGoal for q in self.qlist])
@@ -954,7 +1065,8 @@ class DeviceLoop:
     def __init__(self, x0, vgoal0, gains: dict, horizon: int, n_points: int = 100, *,
                  p_goal=None, rank: int = 0, world: int = 1, dist=None, device=None,
                  model: Model | None = None, seed: int = 1, stream=None, rows: str = "block",
-                 flags: int = LQRO_FLAG_QHULL_ORDER, fence=None, user_planes=None, obstacles=None):
+                 flags: int = LQRO_FLAG_QHULL_ORDER, fence=None, user_planes=None, obstacles=None,
+                 monitor: bool = False):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -983,6 +1095,9 @@ class DeviceLoop:
         # every rank the same set (Context.set_obstacles)
         if obstacles is not None:
             self.set_obstacles(*(obstacles if isinstance(obstacles, tuple) else (obstacles,)))
+        # monitor: every step measures its own rows' clearance on the device (monitor() reads it)
+        if monitor:
+            self.ctx.set_monitor(1)
         self.x = torch.from_numpy(np.ascontiguousarray(x0, np.float64)).to(self.dev)
         self.vgoal = torch.from_numpy(np.ascontiguousarray(vgoal0, np.float64)).to(self.dev)
         self.newv = torch.zeros((n, 3), **f64)
@@ -1018,6 +1133,11 @@ class DeviceLoop:
         """This rank's context takes the hardness level (every rank the same;
         Context.set_hard_planes)."""
         self.ctx.set_hard_planes(level)
+
+    def monitor(self, reset: bool = False):
+        """This rank's (last, since_reset) clearance totals (Context.monitor);
+        merge_clearance joins the ranks'."""
+        return self.ctx.monitor(reset)
 
     def step(self, gather: bool = False):
         """The pair loop for the own rows; newV of the own rows on the device
