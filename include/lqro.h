@@ -612,6 +612,107 @@ int lqro_get_monitor_rows(lqro_ctx* ctx, lqro_clearance_row* rows, int64_t capac
  * the total's n_hit. */
 int lqro_get_monitor_pairs(lqro_ctx* ctx, int64_t* pairs /* 2 per pair */, int64_t capacity, int64_t* n_out);
 
+/* ---- LP audit: what did the LP do with each row's planes? ---------------
+ * An opt-in measurement, on the device, of the step's result against the
+ * plane list each own row's LP saw.  The reference has no counterpart.  For
+ * own row agent i the list is, in this order: the emitted fence faces, the
+ * live user planes (the count clamped to [0, max_per_agent]), then the pair
+ * slots that hold a plane ([6] == 1) in slot order; at LQRO_HARD_OBSTACLES
+ * with obstacles the obstacle slots come first and the agent slots after
+ * (with lqro_set_neighbors the obstacle slots are the entries >= n_agents - 1
+ * of the row's neighbour list).  k is a plane's index in that list, m the
+ * list's length, n_hard the hard prefix the LP used.  With
+ *   v = ((float)newv[3i], (float)newv[3i+1], (float)newv[3i+2]), the step's
+ *   result, and pref = (float)vgoal[3i..],
+ * all fp32, every operation rounded once, no contraction:
+ *   viol_k = n.x (p.x - v.x) + n.y (p.y - v.y) + n.z (p.z - v.z), summed left
+ *            to right: the LP's own violation expression (LQRO:1083, 1138,
+ *            1170); plane k is violated when viol_k > 0
+ *   v2  = v.x v.x + v.y v.y + v.z v.z
+ *   dv2 = d.x d.x + d.y d.y + d.z d.z, d = v - pref
+ * Ties: values compare as fp32 (+0 equals -0); of equal values the lowest k
+ * wins.  kind / id name a plane's source:
+ *   LQRO_AUDIT_FENCE   id = the face 2 a + side, numbered as in the clearance
+ *                      measurement (the real face, not the emitted position)
+ *   LQRO_AUDIT_USER    id = the index among the agent's user planes
+ *   LQRO_AUDIT_COLUMN  id = the column j: an agent, or n_agents + o (without
+ *                      lqro_set_neighbors slot q of row i is column
+ *                      q + (q >= i); with it, the column of the neighbour
+ *                      list's entry)
+ * tol is the caller's tolerance, >= 0 (RVO_EPSILON, 0.00001f, suits a result
+ * the LP reports as feasible).  Inputs must be finite.  The result is
+ * deterministic: (value, k) keys and integer counts, no floating-point
+ * atomics, no dependence on schedule or wave count; a numpy restatement
+ * (tests/lp_audit_ref.py) matches it bit for bit. */
+enum { LQRO_AUDIT_FENCE = 0, LQRO_AUDIT_USER = 1, LQRO_AUDIT_COLUMN = 2 };
+
+typedef struct lqro_lp_row {
+  float viol_max;       /* largest viol_k over the list; -inf for an empty list         */
+  float hard_viol_max;  /* largest viol_k over k < n_hard; -inf when n_hard == 0        */
+  float v2, dv2;        /* |v|^2 and |v - pref|^2                                       */
+  int32_t i;            /* the row's global agent id                                    */
+  int32_t m, n_hard;    /* the list's length and its hard prefix                        */
+  int32_t n_viol;       /* planes with viol_k > 0.0f (linearProgram3's own test)        */
+  int32_t n_viol_tol;   /* planes with viol_k > tol                                     */
+  int32_t n_hard_viol;  /* planes k < n_hard with viol_k > tol                          */
+  int32_t k_viol, kind_viol, id_viol;   /* the plane of viol_max; -1, -1, -1: empty list */
+  int32_t k_hard, kind_hard, id_hard;   /* the plane of hard_viol_max; -1s: n_hard == 0  */
+} lqro_lp_row;
+
+/* Over a context's own rows.  A maximum is decided by the largest value, then
+ * the smallest i, then the smallest k; a -inf maximum has indices -1. */
+typedef struct lqro_lp_total {
+  float viol_max;
+  int32_t viol_i, viol_k, viol_kind, viol_id;
+  float hard_viol_max;
+  int32_t hard_i, hard_k, hard_kind, hard_id;
+  float dv2_max;
+  int32_t dv2_i;
+  int64_t n_rows_viol;       /* rows with n_viol_tol > 0                        */
+  int64_t n_rows_hard_viol;  /* rows with n_hard_viol > 0                       */
+  int64_t n_viol_tol;        /* sum of the rows' n_viol_tol                     */
+  int64_t n_planes;          /* sum of the rows' m                              */
+  int64_t n_measured;        /* audits folded in (1 for a last total)           */
+} lqro_lp_total;
+#ifdef __cplusplus
+static_assert(sizeof(lqro_lp_row) == 64, "lqro_lp_row is 64 bytes");
+static_assert(sizeof(lqro_lp_total) == 88, "lqro_lp_total is 88 bytes");
+#endif
+
+/* on = 1: every lqro_step, lqro_step_device and lqro_step_device_end audits
+ * its own rows at the end of the step, on the step's stream, behind the LP
+ * (and the copy of the rows an early LP ran), reading the caller's d_newv.
+ * Nothing in the step reads the result: newV, records, statistics and the
+ * carried normal are bit-identical to a context without the audit.  The
+ * context keeps two totals on the device: LAST (n_measured = 1) and SINCE
+ * RESET, maxima of maxima (a strictly larger value replaces the kept one, so
+ * the indices are those of the earliest step attaining it) and sums of counts.
+ * on = 0 (the default): no launch, no buffer.  The buffers come from the
+ * context's pool inside this call, after it has waited for the last step, and
+ * never in a step.  LQRO_E_ARG: on outside {0, 1}, tol negative or not
+ * finite; LQRO_E_STATE while a lqro_step_device_begin is pending.  The fence,
+ * user-plane, obstacle, neighbour and hard-plane setters keep the setting and
+ * the since-reset total.  A row shard audits its own rows; the caller merges
+ * the ranks' totals (lqro.py merge_lp_audit; lqro::ShardedSimulator does not). */
+int lqro_set_lp_audit(lqro_ctx* ctx, int32_t on, float tol);
+/* Waits for the last step (like lqro_get_stats), then copies the two totals
+ * (either may be NULL); reset != 0 clears the since-reset total after reading
+ * it.  A context that never audited: both cleared (maxima -inf, indices -1,
+ * counts 0). */
+int lqro_get_lp_audit(lqro_ctx* ctx, lqro_lp_total* last, lqro_lp_total* since_reset, int32_t reset);
+/* The last audit's rows, in own-row order (capacity < the own rows:
+ * LQRO_E_ARG; no audit yet: *n_out = 0). */
+int lqro_get_lp_audit_rows(lqro_ctx* ctx, lqro_lp_row* rows, int64_t capacity, int64_t* n_out);
+/* Without a context, lqro_calculate_new_v_hard's twin: audits newv (n_agents
+ * x 3) against the same plane lists (agent r's planes are planes[6 k ..] for
+ * k in [offsets[r], offsets[r+1]), its first n_hard[r] hard, clamped to the
+ * list's length; n_hard NULL: none), with the same two kernels.  Every plane
+ * has kind LQRO_AUDIT_USER and id = k.  Synchronous.  rows (n_agents) and
+ * total may be NULL. */
+int lqro_audit_new_v(const float* planes, const int64_t* offsets, const int32_t* n_hard /* may be NULL */,
+                     int32_t n_agents, const double* vgoal, const double* newv, float tol,
+                     lqro_lp_row* rows /* may be NULL */, lqro_lp_total* total /* may be NULL */, int32_t device);
+
 /* ---- the per-agent step after the pair loop ------
  * Replaces the agent loop LQRO:1437-1446: vGoal = newV; u = findU()
  * (riccatiControllerSteady, LQRO:594-617); propagateU (propagate,

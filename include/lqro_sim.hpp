@@ -205,6 +205,27 @@ class Simulator {
     return last;
   }
 
+  // The LP audit (lqro_set_lp_audit): with on, every step() measures its
+  // result against each plane the agent's LP saw, on the device; tol >= 0 is
+  // the margin above which a plane counts as violated.  lp_audit() returns
+  // the last step's total and, in *since_reset when given, the one
+  // accumulated since the last reset; rows, when given, receives one record
+  // per agent.  (lqro::ShardedSimulator has no counterpart and does not
+  // merge: a rank reads its own context, the caller merges.)
+  void set_lp_audit(bool on, float tol = 0.0f) { check(lqro_set_lp_audit(ctx_, on ? 1 : 0, tol), "lqro_set_lp_audit"); }
+  lqro_lp_total lp_audit(lqro_lp_total* since_reset = nullptr, bool reset = false,
+                        std::vector<lqro_lp_row>* rows = nullptr) {
+    lqro_lp_total last;
+    if (rows) {
+      rows->resize(q_.size());
+      int64_t n = 0;
+      check(lqro_get_lp_audit_rows(ctx_, rows->data(), (int64_t)rows->size(), &n), "lqro_get_lp_audit_rows");
+      rows->resize((size_t)n);
+    }
+    check(lqro_get_lp_audit(ctx_, &last, since_reset, reset ? 1 : 0), "lqro_get_lp_audit");
+    return last;
+  }
+
   // The pair loop LQRO:1393-1436 on the GPU: every Quadrotor::newV.
   // LQRO_E_HULL (a pair without its half-plane) and LQRO_E_QHMERGE (a pair
   // whose winning facet qconvex's pre-merge may join: its half-plane is not

@@ -121,6 +121,14 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   lqro_clearance_row* d_clrows;   // nrows: the context's own row buffer
   const lqro_clearance_row* cl_last;   // the last measurement's rows: d_clrows or the caller's
   lqro_clearance_total* d_cltot;  // [0] last, [1] since reset
+  // LP audit (lqro_set_lp_audit): allocated by the call that turns it on, never in a step
+  int lp_audit;                   // every step audits its own rows at the end of its tail
+  float audit_tol;
+  int audited;                    // d_aurows holds an audit's rows
+  lqro_lp_row* d_aurows;          // nrows
+  lqro_lp_total* d_autot;         // [0] last, [1] since reset
+  const double* au_vgoal;         // the last tail's vgoal and newV (lqro_debug_lp_audit_times)
+  double* au_newv;
   lqro::PairArgs pa;
   lqro::DevPool mem;              // owns every d_* buffer above that is not the caller's
 };

@@ -85,10 +85,34 @@ struct ClearArgs {
   lqro_clearance_total* tot;    // [0] last, [1] since reset
 };
 
+// The LP audit (lqro_set_lp_audit, lqro_audit_new_v; lqro_kern_audit.hip):
+// the step's result against each own row's plane list, lqro.h's contract.  The
+// list is read through the LpArgs the LP itself was launched with (newv: the
+// result to audit).
+struct LpAuditArgs {
+  float tol;
+  int faces;             // the fence: bit 2 a + side of the emitted faces, for a fence plane's id
+  int plain;             // lqro_audit_new_v: every plane is LQRO_AUDIT_USER with id = k
+  lqro_lp_row* rows;     // nrows records, the own rows in row order
+  lqro_lp_total* tot;    // [0] last, [1] since reset
+};
+
 namespace lqro {
 // k_clear_pack, k_clear, k_clear_total: one measurement (ev: four timing
 // events recorded around the three kernels, scripts/clearance_bench.py; else null)
 void launch_clear(hipStream_t s, const ClearArgs& A, hipEvent_t* ev = nullptr);
+// k_lp_audit, k_lp_audit_total: one audit (ev: three timing events recorded
+// around the two kernels, scripts/lp_audit_bench.py; else null)
+void launch_lp_audit(hipStream_t s, const LpArgs& La, const LpAuditArgs& B, hipEvent_t* ev = nullptr);
+// a total that no audit has touched: maxima -inf, indices -1, counts 0
+inline lqro_lp_total lp_total_none() {
+  lqro_lp_total t{};
+  t.viol_max = t.hard_viol_max = t.dv2_max = -__builtin_huge_valf();
+  t.viol_i = t.viol_k = t.viol_kind = t.viol_id = -1;
+  t.hard_i = t.hard_k = t.hard_kind = t.hard_id = -1;
+  t.dv2_i = -1;
+  return t;
+}
 struct HullArgs;
 struct ObsSlots;   // (lqro_hull_job.hpp)
 // k_tables: one workgroup per agent with gains of its own (n_gains: 1 or N)

@@ -2,6 +2,7 @@
 // version and status text, the default configuration, gain synthesis, the
 // agents' dynamics step and the stand-alone LP.  Their device buffers live in
 // a DevPool on the stack (lqro_devmem.hpp), so every return frees them.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -168,6 +169,27 @@ int lqro_dynamics_step(const lqro_model* models, int32_t n_models, int32_t n, in
   return LQRO_OK;
 }
 
+// The stand-alone LP's and audit's slot layout: agent r's planes as k_pair's
+// 32-byte slots ([6] = 1), every row at the pitch of the longest list (one
+// slot at least).  LQRO_E_ARG for a list of negative length.
+static int plane_slots(const float* planes, const int64_t* offsets, int n_agents, int64_t& mmax, std::vector<float>& h) {
+  mmax = 1;
+  for (int r = 0; r < n_agents; ++r) {
+    const int64_t m = offsets[r + 1] - offsets[r];
+    if (m < 0) return LQRO_E_ARG;
+    if (m > mmax) mmax = m;
+  }
+  h.assign((size_t)n_agents * (size_t)mmax * 8, 0.0f);
+  for (int r = 0; r < n_agents; ++r)
+    for (int64_t k = offsets[r]; k < offsets[r + 1]; ++k) {
+      float* d = &h[((size_t)r * mmax + (size_t)(k - offsets[r])) * 8];
+      for (int q = 0; q < 6; ++q) d[q] = planes[6 * k + q];
+      int one = 1;
+      memcpy(&d[6], &one, 4);
+    }
+  return LQRO_OK;
+}
+
 int lqro_calculate_new_v(const float* planes, const int64_t* offsets, int32_t n_agents,
                          const double* vgoal, double vmax_lp, double* newv, int32_t device) {
   return lqro_calculate_new_v_hard(planes, offsets, nullptr, n_agents, vgoal, vmax_lp, newv, device);
@@ -181,21 +203,10 @@ int lqro_calculate_new_v_hard(const float* planes, const int64_t* offsets, const
     for (int r = 0; r < n_agents; ++r)
       if (n_hard[r] < 0) return LQRO_E_ARG;
   HIPCHK(hipSetDevice(device));
-  int64_t mmax = 1;
-  for (int r = 0; r < n_agents; ++r) {
-    const int64_t m = offsets[r + 1] - offsets[r];
-    if (m < 0) return LQRO_E_ARG;
-    if (m > mmax) mmax = m;
-  }
+  int64_t mmax;
+  std::vector<float> h;
+  if (int rc = plane_slots(planes, offsets, n_agents, mmax, h)) return rc;
   const size_t slots = (size_t)n_agents * (size_t)mmax;
-  std::vector<float> h(slots * 8, 0.0f);
-  for (int r = 0; r < n_agents; ++r)
-    for (int64_t k = offsets[r]; k < offsets[r + 1]; ++k) {
-      float* d = &h[((size_t)r * mmax + (size_t)(k - offsets[r])) * 8];
-      for (int q = 0; q < 6; ++q) d[q] = planes[6 * k + q];
-      int one = 1;
-      memcpy(&d[6], &one, 4);
-    }
   DevPool mem;
   float *d_slots = nullptr, *d_compact = nullptr, *d_proj = nullptr;
   double *d_vg = nullptr, *d_nv = nullptr;
@@ -216,6 +227,51 @@ int lqro_calculate_new_v_hard(const float* planes, const int64_t* offsets, const
   La.obs_first = -1; La.nhard_rows = d_nh;   // (the kernel clamps to the row's plane count)
   if (launch_lp(La, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
       hipMemcpy(newv, d_nv, sizeof(double) * 3 * n_agents, hipMemcpyDeviceToHost) != hipSuccess)
+    return LQRO_E_HIP;
+  return LQRO_OK;
+}
+
+// lqro_calculate_new_v_hard's twin: the same slot layout and n_hard clamping
+// (in the kernel), the audit's two kernels in place of the LP's
+int lqro_audit_new_v(const float* planes, const int64_t* offsets, const int32_t* n_hard, int32_t n_agents,
+                     const double* vgoal, const double* newv, float tol, lqro_lp_row* rows, lqro_lp_total* total,
+                     int32_t device) {
+  if (!planes || !offsets || !vgoal || !newv || n_agents <= 0 || !(tol >= 0.0f) || !std::isfinite(tol))
+    return LQRO_E_ARG;
+  if (n_hard)
+    for (int r = 0; r < n_agents; ++r)
+      if (n_hard[r] < 0) return LQRO_E_ARG;
+  int64_t mmax;
+  std::vector<float> h;
+  if (int rc = plane_slots(planes, offsets, n_agents, mmax, h)) return rc;
+  const size_t slots = (size_t)n_agents * (size_t)mmax;
+  HIPCHK(hipSetDevice(device));
+  DevPool mem;
+  float* d_slots = nullptr;
+  double *d_vg = nullptr, *d_nv = nullptr;
+  int* d_nh = nullptr;
+  lqro_lp_row* d_rows = nullptr;
+  lqro_lp_total* d_tot = nullptr;
+  if (mem.get(d_slots, 8 * slots) || mem.get(d_vg, 3 * (size_t)n_agents) || mem.get(d_nv, 3 * (size_t)n_agents) ||
+      mem.get(d_rows, (size_t)n_agents) || mem.get(d_tot, 2) || (n_hard && mem.get(d_nh, (size_t)n_agents)))
+    return LQRO_E_NOMEM;
+  const lqro_lp_total none[2] = {lp_total_none(), lp_total_none()};
+  if ((n_hard && hipMemcpy(d_nh, n_hard, sizeof(int) * (size_t)n_agents, hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(d_slots, h.data(), sizeof(float) * 8 * slots, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_vg, vgoal, sizeof(double) * 3 * n_agents, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_nv, newv, sizeof(double) * 3 * n_agents, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_tot, none, sizeof none, hipMemcpyHostToDevice) != hipSuccess)
+    return LQRO_E_HIP;
+  LpArgs La{};
+  La.npr = (int)mmax; La.cap = (int)mmax; La.nrows = n_agents; La.row_begin = 0; La.row_stride = 1;
+  La.slots = d_slots; La.vgoal = d_vg; La.newv = d_nv;
+  La.obs_first = -1; La.nhard_rows = d_nh;
+  LpAuditArgs B{};
+  B.tol = tol; B.plain = 1; B.rows = d_rows; B.tot = d_tot;
+  launch_lp_audit(0, La, B);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      (rows && hipMemcpy(rows, d_rows, sizeof(lqro_lp_row) * (size_t)n_agents, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (total && hipMemcpy(total, d_tot, sizeof *total, hipMemcpyDeviceToHost) != hipSuccess))
     return LQRO_E_HIP;
   return LQRO_OK;
 }

@@ -641,6 +641,14 @@ static LpArgs lp_args(const lqro_ctx* c, int npr, const double* d_vgoal, double*
   return La;
 }
 
+// the LP audit's own arguments (lqro_set_lp_audit)
+static LpAuditArgs audit_args(const lqro_ctx* c) {
+  LpAuditArgs B{};
+  B.tol = c->audit_tol; B.faces = c->nfence > 0 ? c->fence_faces : 0; B.plain = 0;
+  B.rows = c->d_aurows; B.tot = c->d_autot;
+  return B;
+}
+
 // what the planner reads of the context and of the kernels' headers
 // (d_lpnv: where an early LP would write, d_newv: the caller's buffer)
 static StepShape step_shape(const lqro_ctx* c, int phase, const double* d_lpnv, const double* d_newv) {
@@ -969,6 +977,12 @@ static int enqueue_tail(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   if (c->early_step && c->early_internal && d_newv != c->d_newv) {   // the rows the early LP ran, into the caller's newV
     LAUNCH(launch_copy_claimed(s, c->d_rowclaim, c->nrows, c->rb, c->rs, c->d_newv, d_newv));
   }
+  // the audit: this step's result against the lists its LP read; nothing in the step reads it
+  c->au_vgoal = d_vgoal; c->au_newv = d_newv;
+  if (c->lp_audit) {
+    LAUNCH(launch_lp_audit(s, lp_args(c, npr, d_vgoal, d_newv), audit_args(c)));
+    c->audited = 1;
+  }
   // this step's work, for the schedule of the step two after it
   StepFeedback* fb = c->h_feedback + slot;
   static_assert(offsetof(StepFeedback, build_max) - offsetof(StepFeedback, sweep_work) ==
@@ -1254,6 +1268,79 @@ int lqro_get_monitor_pairs(lqro_ctx* c, int64_t* pairs, int64_t cap, int64_t* n_
     }
   *n_out = n;
   return LQRO_OK;
+}
+
+// ---- LP audit --------------------------------------------------------------
+int lqro_set_lp_audit(lqro_ctx* c, int32_t on, float tol) {
+  if (!c || (on != 0 && on != 1) || !(tol >= 0.0f) || !std::isfinite(tol)) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;   // the pending half-step's tail audits, or does not, as it was set
+  if (int rc = ctx_enter(c, false)) return rc;
+  if (on && !c->d_autot) {   // the buffers, once: after the last step, never in a step
+    lqro_lp_row* rows = nullptr;
+    lqro_lp_total* tot = nullptr;
+    if (c->mem.get(rows, (size_t)c->nrows) || c->mem.get(tot, 2)) {
+      c->mem.release(rows);
+      return LQRO_E_NOMEM;
+    }
+    const lqro_lp_total t[2] = {lp_total_none(), lp_total_none()};
+    if (hipMemcpy(tot, t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) {
+      c->mem.release(rows); c->mem.release(tot);
+      return LQRO_E_HIP;
+    }
+    c->d_aurows = rows; c->d_autot = tot;
+  }
+  c->lp_audit = on;
+  if (on) c->audit_tol = tol;
+  return LQRO_OK;
+}
+
+int lqro_get_lp_audit(lqro_ctx* c, lqro_lp_total* last, lqro_lp_total* since_reset, int32_t reset) {
+  if (!c) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;   // (pending: the half-step's audit comes with its _end)
+  lqro_lp_total t[2] = {lp_total_none(), lp_total_none()};
+  if (c->d_autot) HIPCHK(hipMemcpy(t, c->d_autot, sizeof t, hipMemcpyDeviceToHost));
+  if (last) *last = t[0];
+  if (since_reset) *since_reset = t[1];
+  if (reset && c->d_autot) {
+    const lqro_lp_total none = lp_total_none();
+    HIPCHK(hipMemcpy(c->d_autot + 1, &none, sizeof none, hipMemcpyHostToDevice));
+  }
+  return LQRO_OK;
+}
+
+int lqro_get_lp_audit_rows(lqro_ctx* c, lqro_lp_row* rows, int64_t cap, int64_t* n_out) {
+  if (!c || !n_out || (cap > 0 && !rows)) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  *n_out = 0;
+  if (!c->audited) return LQRO_OK;
+  if (cap < c->nrows) return LQRO_E_ARG;
+  HIPCHK(hipMemcpy(rows, c->d_aurows, sizeof(lqro_lp_row) * (size_t)c->nrows, hipMemcpyDeviceToHost));
+  *n_out = c->nrows;
+  return LQRO_OK;
+}
+
+// scripts/lp_audit_bench.py: the last step's audit once more on the context's
+// stream, an audit like any other (it folds into the totals), with the two
+// kernels' own times from HIP events (ms: k_lp_audit, k_lp_audit_total).
+// Synchronous; declared where it is used, like the lqro_debug_* hooks.
+int lqro_debug_lp_audit_times(lqro_ctx* c, float* ms2) {
+  if (!c || !ms2) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  if (!c->lp_audit || !c->audited) return LQRO_E_STATE;
+  const int npr = c->nbr_k > 0 ? std::min(c->nbr_k, c->npr) : c->npr;
+  hipEvent_t ev[3] = {};
+  int rc = LQRO_OK;
+  for (int k = 0; k < 3 && rc == LQRO_OK; ++k)
+    if (hipEventCreate(&ev[k]) != hipSuccess) rc = LQRO_E_HIP;
+  if (rc == LQRO_OK) {
+    launch_lp_audit(c->stream, lp_args(c, npr, c->au_vgoal, c->au_newv), audit_args(c), ev);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) rc = LQRO_E_HIP;
+  }
+  for (int k = 0; k < 2 && rc == LQRO_OK; ++k)
+    if (hipEventElapsedTime(&ms2[k], ev[k], ev[k + 1]) != hipSuccess) rc = LQRO_E_HIP;
+  for (int k = 0; k < 3; ++k)
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+  return rc;
 }
 
 int lqro_set_carry_normal(lqro_ctx* c, const double* n3) {

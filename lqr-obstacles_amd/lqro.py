@@ -120,6 +120,76 @@ def merge_clearance(totals) -> dict:
     return out
 
 
+class LpRow(C.Structure):
+    """lqro_lp_row: one own row's result against the plane list its LP saw."""
+    _fields_ = [("viol_max", C.c_float), ("hard_viol_max", C.c_float), ("v2", C.c_float), ("dv2", C.c_float),
+                ("i", C.c_int32), ("m", C.c_int32), ("n_hard", C.c_int32), ("n_viol", C.c_int32),
+                ("n_viol_tol", C.c_int32), ("n_hard_viol", C.c_int32),
+                ("k_viol", C.c_int32), ("kind_viol", C.c_int32), ("id_viol", C.c_int32),
+                ("k_hard", C.c_int32), ("kind_hard", C.c_int32), ("id_hard", C.c_int32)]
+
+
+class LpTotal(C.Structure):
+    """lqro_lp_total: the maxima and counts over a context's own rows."""
+    _fields_ = [("viol_max", C.c_float), ("viol_i", C.c_int32), ("viol_k", C.c_int32), ("viol_kind", C.c_int32),
+                ("viol_id", C.c_int32),
+                ("hard_viol_max", C.c_float), ("hard_i", C.c_int32), ("hard_k", C.c_int32), ("hard_kind", C.c_int32),
+                ("hard_id", C.c_int32),
+                ("dv2_max", C.c_float), ("dv2_i", C.c_int32),
+                ("n_rows_viol", C.c_int64), ("n_rows_hard_viol", C.c_int64), ("n_viol_tol", C.c_int64),
+                ("n_planes", C.c_int64), ("n_measured", C.c_int64)]
+
+
+LP_ROW_DTYPE = np.dtype([("viol_max", "<f4"), ("hard_viol_max", "<f4"), ("v2", "<f4"), ("dv2", "<f4"),
+                         ("i", "<i4"), ("m", "<i4"), ("n_hard", "<i4"), ("n_viol", "<i4"), ("n_viol_tol", "<i4"),
+                         ("n_hard_viol", "<i4"), ("k_viol", "<i4"), ("kind_viol", "<i4"), ("id_viol", "<i4"),
+                         ("k_hard", "<i4"), ("kind_hard", "<i4"), ("id_hard", "<i4")])
+assert LP_ROW_DTYPE.itemsize == C.sizeof(LpRow) == 64 and C.sizeof(LpTotal) == 88
+LP_TOTAL_FIELDS = tuple(n for n, _ in LpTotal._fields_)
+# a plane's source in an LP audit record (lqro.h)
+LQRO_AUDIT_FENCE, LQRO_AUDIT_USER, LQRO_AUDIT_COLUMN = 0, 1, 2
+RVO_EPSILON = 0.00001   # the tolerance the docs suggest for set_lp_audit
+
+
+def _lp_total_dict(t: LpTotal) -> dict:
+    return {n: getattr(t, n) for n in LP_TOTAL_FIELDS}
+
+
+_LP_MAXIMA = (("viol_max", ("viol_i", "viol_k", "viol_kind", "viol_id")),
+              ("hard_viol_max", ("hard_i", "hard_k", "hard_kind", "hard_id")),
+              ("dv2_max", ("dv2_i",)))
+_LP_COUNTS = ("n_rows_viol", "n_rows_hard_viol", "n_viol_tol", "n_planes")
+
+
+def merge_lp_audit(totals) -> dict:
+    """The ranks' totals of one audit (or of the same audits since a reset) as
+    one: each maximum is decided by the largest value, then the smallest i,
+    then the smallest k over the shards (a -inf maximum has indices -1), the
+    counts are summed, n_measured is the shards' common count (its largest).
+    Row shards partition the rows, so the merge of a block or cyclic split
+    equals the single context's total of one audit."""
+    totals = list(totals)
+    out = {n: (0 if n.startswith("n_") else -1) for n in LP_TOTAL_FIELDS}
+    for v, idx in _LP_MAXIMA:
+        out[v] = np.float32(-np.inf)
+        best = None
+        for t in totals:
+            val = np.float32(t[v])
+            if not val > -np.inf:
+                continue
+            key = (int(t[idx[0]]), int(t[idx[1]]) if len(idx) > 1 else 0)
+            if best is None or val > best[0] or (val == best[0] and key < best[1]):
+                best = (val, key, t)
+        if best is not None:
+            out[v] = best[0]
+            for n in idx:
+                out[n] = int(best[2][n])
+    for k in _LP_COUNTS:
+        out[k] = sum(int(t[k]) for t in totals)
+    out["n_measured"] = max([int(t["n_measured"]) for t in totals], default=0)
+    return out
+
+
 # every symbol include/lqro.h declares
 EXPORTS = (
     "lqro_config_default", "lqro_model_default", "lqro_synthesize_gains", "lqro_sphere",
@@ -137,6 +207,7 @@ EXPORTS = (
     "lqro_set_hard_planes", "lqro_calculate_new_v_hard",
     "lqro_clearance", "lqro_clearance_device", "lqro_set_monitor", "lqro_get_monitor",
     "lqro_get_monitor_rows", "lqro_get_monitor_pairs",
+    "lqro_set_lp_audit", "lqro_get_lp_audit", "lqro_get_lp_audit_rows", "lqro_audit_new_v",
 )
 # lqro_set_hard_planes' levels: the planes linearProgram4 does not relax
 LQRO_HARD_NONE, LQRO_HARD_FENCE, LQRO_HARD_HEAD, LQRO_HARD_OBSTACLES = 0, 1, 2, 3
@@ -209,6 +280,11 @@ def lib() -> C.CDLL:
             L.lqro_get_monitor.argtypes = [vp, C.POINTER(ClearanceTotal), C.POINTER(ClearanceTotal), i32]
             L.lqro_get_monitor_rows.argtypes = [vp, vp, i64, C.POINTER(i64)]
             L.lqro_get_monitor_pairs.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        if hasattr(L, "lqro_set_lp_audit"):   # (older libraries in A/B runs lack them)
+            L.lqro_set_lp_audit.argtypes = [vp, i32, C.c_float]
+            L.lqro_get_lp_audit.argtypes = [vp, C.POINTER(LpTotal), C.POINTER(LpTotal), i32]
+            L.lqro_get_lp_audit_rows.argtypes = [vp, vp, i64, C.POINTER(i64)]
+            L.lqro_audit_new_v.argtypes = [vp, vp, vp, i32, vp, vp, C.c_float, vp, C.POINTER(LpTotal), i32]
         L.lqro_set_carry_normal.argtypes = [vp, vp]
         L.lqro_get_carry_normal.argtypes = [vp, vp]
         _lib = L
@@ -510,6 +586,30 @@ class Context:
         _check(lib().lqro_get_monitor_pairs(self._h, _p(out), len(out), C.byref(n)), "lqro_get_monitor_pairs")
         return out[:n.value]
 
+    def set_lp_audit(self, on, tol: float = 0.0):
+        """on: every step audits its own rows at its end, on the step's
+        stream: the result against each plane the row's LP saw
+        (lqro_set_lp_audit; lqro.h states the formulas); the step's results do
+        not change.  tol >= 0: the margin above which a plane counts as
+        violated (RVO_EPSILON suits).  Off: no launch."""
+        _check(lib().lqro_set_lp_audit(self._h, int(on), float(tol)), "lqro_set_lp_audit")
+
+    def lp_audit(self, reset: bool = False):
+        """(last, since_reset) LP-audit totals as dicts, after waiting for the
+        last step (lqro_get_lp_audit); reset clears the since-reset total
+        after reading it."""
+        a, b = LpTotal(), LpTotal()
+        _check(lib().lqro_get_lp_audit(self._h, C.byref(a), C.byref(b), int(bool(reset))), "lqro_get_lp_audit")
+        return _lp_total_dict(a), _lp_total_dict(b)
+
+    def lp_audit_rows(self) -> np.ndarray:
+        """The last audit's rows, an LP_ROW_DTYPE array in own-row order
+        (empty before the first)."""
+        rows = np.zeros(len(self.row_ids), dtype=LP_ROW_DTYPE)
+        n = C.c_int64()
+        _check(lib().lqro_get_lp_audit_rows(self._h, _p(rows), len(rows), C.byref(n)), "lqro_get_lp_audit_rows")
+        return rows[:n.value]
+
     def set_gains(self, A, B, L, E, per_agent: bool = False):
         A, B, L, E = (np.ascontiguousarray(v, dtype=np.float64) for v in (A, B, L, E))
         X, U, n = self.cfg.x_dim, self.cfg.u_dim, self.cfg.n_agents
@@ -670,6 +770,30 @@ def calculate_new_v(plane_lists, vgoals, vmax_lp: float = 100.0, device: int = 0
     _check(lib().lqro_calculate_new_v(_p(flat), _p(offs), n, _p(vg), vmax_lp, _p(out), device),
            "lqro_calculate_new_v")
     return out
+
+
+def audit_new_v(plane_lists, vgoals, newv, tol: float = 0.0, n_hard=None, device: int = 0):
+    """The LP audit without a context (lqro_audit_new_v), calculate_new_v's
+    twin: newv ((n, 3)) against the same plane lists, agent r's first
+    n_hard[r] planes hard (clamped; None: none).  Returns (rows, total): an
+    LP_ROW_DTYPE array and the total as a dict; every plane has kind
+    LQRO_AUDIT_USER and id = k."""
+    n = len(plane_lists)
+    offs = np.zeros(n + 1, dtype=np.int64)
+    for r, p in enumerate(plane_lists):
+        offs[r + 1] = offs[r] + len(p)
+    flat = np.zeros((max(int(offs[-1]), 1), 6), dtype=np.float32)
+    for r, p in enumerate(plane_lists):
+        if len(p):
+            flat[offs[r]:offs[r + 1]] = np.asarray(p, dtype=np.float32).reshape(-1, 6)
+    vg = np.ascontiguousarray(vgoals, dtype=np.float64).reshape(n, 3)
+    nv = np.ascontiguousarray(newv, dtype=np.float64).reshape(n, 3)
+    nh = None if n_hard is None else np.ascontiguousarray(n_hard, dtype=np.int32).reshape(n)
+    rows = np.zeros(n, dtype=LP_ROW_DTYPE)
+    t = LpTotal()
+    _check(lib().lqro_audit_new_v(_p(flat), _p(offs), None if nh is None else _p(nh), n, _p(vg), _p(nv), float(tol),
+                                  _p(rows), C.byref(t), device), "lqro_audit_new_v")
+    return rows, _lp_total_dict(t)
 
 
 # ---------------------------------------------------------------------------
@@ -906,6 +1030,14 @@ class Simulator:
         """Context.clearance on the agents' current estimates q.x."""
         return self.ctx.clearance(np.stack([q.x for q in self.qlist]))
 
+    def set_lp_audit(self, on, tol: float = 0.0):
+        """Every step() audits its LP's result on the device (Context.set_lp_audit)."""
+        self.ctx.set_lp_audit(on, tol)
+
+    def lp_audit(self, reset: bool = False):
+        """(last, since_reset) totals of the steps' LP audits (Context.lp_audit)."""
+        return self.ctx.lp_audit(reset)
+
     def step(self):
         x = np.stack([q.x for q in self.qlist])
         vg = np.stack([q.vGoal for q in self.qlist])
@@ -1066,7 +1198,7 @@ class DeviceLoop:
                  p_goal=None, rank: int = 0, world: int = 1, dist=None, device=None,
                  model: Model | None = None, seed: int = 1, stream=None, rows: str = "block",
                  flags: int = LQRO_FLAG_QHULL_ORDER, fence=None, user_planes=None, obstacles=None,
-                 monitor: bool = False):
+                 monitor: bool = False, lp_audit=False):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -1098,6 +1230,10 @@ class DeviceLoop:
         # monitor: every step measures its own rows' clearance on the device (monitor() reads it)
         if monitor:
             self.ctx.set_monitor(1)
+        # lp_audit: every step audits its own rows' LP result on the device (lp_audit() reads it);
+        # True, or the tolerance itself
+        if lp_audit is not False and lp_audit is not None:
+            self.ctx.set_lp_audit(1, 0.0 if lp_audit is True else float(lp_audit))
         self.x = torch.from_numpy(np.ascontiguousarray(x0, np.float64)).to(self.dev)
         self.vgoal = torch.from_numpy(np.ascontiguousarray(vgoal0, np.float64)).to(self.dev)
         self.newv = torch.zeros((n, 3), **f64)
@@ -1138,6 +1274,11 @@ class DeviceLoop:
         """This rank's (last, since_reset) clearance totals (Context.monitor);
         merge_clearance joins the ranks'."""
         return self.ctx.monitor(reset)
+
+    def lp_audit(self, reset: bool = False):
+        """This rank's (last, since_reset) LP-audit totals (Context.lp_audit);
+        merge_lp_audit joins the ranks'."""
+        return self.ctx.lp_audit(reset)
 
     def step(self, gather: bool = False):
         """The pair loop for the own rows; newV of the own rows on the device
