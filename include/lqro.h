@@ -389,6 +389,64 @@ int lqro_set_obstacles_ex_device(lqro_ctx* ctx, const double* d_states /* M*X, r
 #define LQRO_HARD_OBSTACLES 3
 int lqro_set_hard_planes(lqro_ctx* ctx, int32_t level);
 
+/* ---- activity mask: agents that leave and rejoin the swarm ----------------
+ * A context's swarm is n_agents bodies for its whole life; the mask says
+ * which of them take part in a step.  The reference has no counterpart: its
+ * NUM_QUADS is a compile-time constant (LQRO:9).  active[i] != 0: agent i
+ * takes part; N bytes indexed by the global agent id (every row shard takes
+ * the same array).  An inactive agent is neither a row nor a column of the
+ * step: the step over N agents with mask a equals the step over the compacted
+ * swarm x[a], vgoal[a], the per-agent tables [a] and the same obstacles, rows
+ * and columns in their relative order.
+ *   - Columns.  In an active row the slot of an inactive column holds no
+ *     plane: its flag is written as 0 this step, whatever an earlier step left
+ *     there.  The column adds no hull job, no hull-build record and nothing to
+ *     the counters, and is never named by lqro_get_hull_failures or
+ *     lqro_get_qhmerge_pairs.  Obstacle columns (j >= n_agents) are not masked.
+ *   - Rows.  An inactive own row does no pair work and no LP and gets no fence
+ *     or user planes; newv[3i..3i+2] is written as +0.0 by lqro_step,
+ *     lqro_step_device and lqro_step_device_end alike; its entry of the
+ *     n_agents x 4 row-normal table is that of a row without a plane.
+ *   - The carried normal runs through the active pairs in (i, j) order; a step
+ *     without an active pair leaves it as it entered.
+ *   - Records (LQRO_FLAG_RECORDS): the count and the slot numbering do not
+ *     change (slot q of row i is column q + (q >= i)); a slot whose row or
+ *     column is inactive has i and j set and every other field zero.
+ *   - lqro_get_stats()[0] counts the slots visited: for each active own row the
+ *     active columns other than itself plus the obstacle columns (with
+ *     lqro_set_neighbors the kept neighbours, as before).
+ *   - Slot numbers do not move (unlike lqro_set_obstacles), so what the
+ *     schedule keeps per slot stays valid; a pair it carried over from the last
+ *     step whose row or column is now inactive is dropped at the head of the
+ *     step, before anything is built for it.  The schedule is planned for
+ *     n_agents whatever the mask (a device mask's count is known on the device
+ *     only); results do not depend on it.
+ *   - lqro_set_neighbors: inactive agents are no candidates; K stays
+ *     min(max_neighbors, n_agents - 1 + M); an inactive row's list is all -1.
+ *   - Clearance (the monitor and lqro_clearance[_device]): inactive agents are
+ *     neither measured rows nor columns; an inactive own row's record is the
+ *     cleared one (minima +inf, indices -1, n_hit 0, hit[] -1) and adds nothing
+ *     to the totals.  The explicit calls read the mask when they run.
+ *   - LP audit: an inactive own row's record is the cleared one (i set, m =
+ *     n_hard = 0, maxima -inf with indices -1, counts 0, v2 = dv2 = 0) and the
+ *     row is left out of every total, dv2_max included.
+ *   - lqro_calculate_new_v*, lqro_audit_new_v and lqro_dynamics_step* take no
+ *     context and do not see the mask.
+ * NULL clears: the context is then the one that never had a mask, in every
+ * launch, size and result; an all-ones mask gives bit-identical results too.
+ * The host form copies the bytes.  The device form keeps the pointer: the
+ * bytes are read on the step's stream when the step runs, so the caller keeps
+ * them alive and may rewrite them there before every step
+ * (lqro_set_obstacles_device's contract).  Both wait for the last enqueued
+ * step, return LQRO_E_STATE while a lqro_step_device_begin is pending and
+ * LQRO_E_ARG for a null context, allocate nothing inside a step, and leave the
+ * context as it was when they fail.  The mask stays when obstacles, fence, user
+ * planes, neighbours, hard planes, monitor or audit are set or cleared, and
+ * setting it keeps all of those and the since-reset totals.  lqro_version()
+ * does not change: callers detect the feature by the symbol. */
+int lqro_set_active(lqro_ctx* ctx, const uint8_t* active /* N, host, copied */);
+int lqro_set_active_device(lqro_ctx* ctx, const uint8_t* d_active /* N, read when the step runs */);
+
 /* One control step: the pair loop LQRO:1393-1436 for the context's rows.
  * x: n_agents*X agent states (Quadrotor::x), vgoal: n_agents*3,
  * newv: n_agents*3 (only rows [row_begin,row_end) are written).  Host

@@ -205,6 +205,15 @@ class ShardedSimulator {
     if (ctx_) check(lqro_set_hard_planes(ctx_, level), "lqro_set_hard_planes");
   }
 
+  // Simulator::setActive for this rank's context: every rank passes the same
+  // global array, one byte per agent of the swarm (lqro_set_active); an empty
+  // vector clears.  The mask governs the avoidance step alone: iterate() goes
+  // on propagating every own agent.
+  void setActive(const std::vector<uint8_t>& active) {
+    if (!active.empty() && active.size() != (size_t)n_) throw std::runtime_error("setActive: one byte per agent");
+    if (ctx_) check(lqro_set_active(ctx_, active.empty() ? nullptr : active.data()), "lqro_set_active");
+  }
+
   // One iteration of LQRO:1393-1446 for this rank's rows, then the state
   // exchange; returns the next seed of the rand() stream.  Enqueued only:
   // download() waits for it.

@@ -184,6 +184,16 @@ class Simulator {
   // default) is the reference's LP.
   void setHardPlanes(int32_t level) { check(lqro_set_hard_planes(ctx_, level), "lqro_set_hard_planes"); }
 
+  // The activity mask (lqro_set_active): active[i] != 0, agent i takes part in
+  // the steps that follow; an inactive agent is neither a row nor a column of
+  // the pair loop (nobody avoids it), and step() leaves its newV at zero.  One
+  // byte per agent; an empty vector clears (everybody takes part); another
+  // size throws.  update() goes on propagating every agent.
+  void setActive(const std::vector<uint8_t>& active) {
+    if (!active.empty() && active.size() != q_.size()) throw std::runtime_error("setActive: one byte per agent");
+    check(lqro_set_active(ctx_, active.empty() ? nullptr : active.data()), "lqro_set_active");
+  }
+
   // Clearance (lqro_clearance): how clear every agent's current estimate
   // Quadrotor::x is of every other agent and obstacle, and of the fence;
   // rows, when given, receives one record per agent.  Returns the total.

@@ -129,6 +129,11 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   lqro_lp_total* d_autot;         // [0] last, [1] since reset
   const double* au_vgoal;         // the last tail's vgoal and newV (lqro_debug_lp_audit_times)
   double* au_newv;
+  // activity mask (lqro_set_active[_device]): allocated by the setter, never in a step
+  const unsigned char* d_actsrc;  // n_agents bytes: the caller's, or d_actown (null: no mask)
+  unsigned char* d_actown;        // lqro_set_active's copy
+  unsigned char* d_act;           // k_active's 0 / 1 bytes, padded to a multiple of 4: what the step's kernels read
+  int act_step;                   // the last step ran under a mask (its pairs counter is k_active's)
   lqro::PairArgs pa;
   lqro::DevPool mem;              // owns every d_* buffer above that is not the caller's
 };

@@ -120,6 +120,17 @@ __device__ __forceinline__ double uniform(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
+// The activity mask (lqro_set_active) as the step's kernels read it: k_active's
+// 0 / 1 bytes, the array padded to whole words.  agent_on_u is for an agent id
+// every lane holds alike (k_pair: a wave takes one pair): one scalar load of
+// the byte's word (the bytes do not change while the step's kernels run).
+__device__ __forceinline__ bool agent_on_u(const unsigned char* act, int agent) {
+  typedef const unsigned int __attribute__((address_space(4))) cword;
+  const int a = __builtin_amdgcn_readfirstlane(agent);
+  const unsigned int w = ((cword*)(const void*)act)[a >> 2];
+  return ((w >> (8 * (a & 3))) & 0xFFu) != 0u;
+}
+
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();

@@ -53,6 +53,10 @@ struct LpArgs {
   int hard, obs_first;
   const int* nbr;
   const int* nhard_rows;
+  // activity mask (lqro_set_active; k_active's byte per agent, null: none):
+  // an inactive own row's LP is not run, its newV is +0.0; the audit gives it
+  // the cleared record and leaves it out of the totals
+  const unsigned char* active;
 };
 
 // The fence (lqro_set_fence): an axis-aligned box [lo, hi] the agents'
@@ -83,6 +87,11 @@ struct ClearArgs {
   double lo[3], hi[3], m[3];
   lqro_clearance_row* rows;     // nrows records, the own rows in row order
   lqro_clearance_total* tot;    // [0] last, [1] since reset
+  // activity mask (lqro_set_active; null: none): the caller's n_agents bytes
+  // as they are when the measurement runs (!= 0: takes part).  An inactive
+  // agent is neither a measured row nor a column; its own row's record is the
+  // cleared one, which adds nothing to the totals
+  const unsigned char* active;
 };
 
 // The LP audit (lqro_set_lp_audit, lqro_audit_new_v; lqro_kern_audit.hip):

@@ -106,6 +106,16 @@ __global__ void __launch_bounds__(256) k_lp_audit(LpArgs A, LpAuditArgs B) {
   const int lrow = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (lrow >= A.nrows) return;   // (wave-uniform)
   const int i = A.row_begin + lrow * A.row_stride;
+  if (A.active != nullptr && A.active[i] == 0) {   // not in this step (lqro_set_active): the cleared record
+    if (lane != 0) return;
+    const int ninf_bits = __float_as_int(-__builtin_huge_valf());
+    int4* o = reinterpret_cast<int4*>(B.rows + lrow);
+    o[0] = make_int4(ninf_bits, ninf_bits, 0, 0);
+    o[1] = make_int4(i, 0, 0, 0);
+    o[2] = make_int4(0, 0, -1, -1);
+    o[3] = make_int4(-1, -1, -1, -1);
+    return;
+  }
   const v3 v = V3((float)A.newv[3 * i], (float)A.newv[3 * i + 1], (float)A.newv[3 * i + 2]);
   const v3 pref = V3((float)A.vgoal[3 * i], (float)A.vgoal[3 * i + 1], (float)A.vgoal[3 * i + 2]);
   const float ninf = -__builtin_huge_valf();
@@ -189,6 +199,7 @@ __global__ void __launch_bounds__(256) k_lp_audit_total(LpArgs A, LpAuditArgs B)
   long long rv = 0, rh = 0, vt = 0, pl = 0;
   for (int lrow = tid; lrow < A.nrows; lrow += 256) {
     const lqro_lp_row R = B.rows[lrow];
+    if (A.active != nullptr && A.active[R.i] == 0) continue;   // (its dv2 = 0 is no measurement)
     const AuKey a{R.viol_max, R.i, R.k_viol, R.kind_viol, R.id_viol};
     const AuKey h{R.hard_viol_max, R.i, R.k_hard, R.kind_hard, R.id_hard};
     const AuKey d{R.dv2, R.i, 0, -1, -1};

@@ -62,7 +62,7 @@ __device__ __forceinline__ bool cl_less(double v, int j, double bv, int bj) {
 // column order until six are found.
 __global__ void __launch_bounds__(CL_BLOCK) k_clear(ClearArgs A) {
   __shared__ double sp[3][CL_TR];
-  __shared__ int si[CL_TR];
+  __shared__ int si[CL_TR], s_on[CL_TR];   // s_on: the row takes part (lqro_set_active)
   __shared__ double w_s2[CL_WAVES][CL_TR], w_d2[CL_WAVES][CL_TR];
   __shared__ int w_js[CL_WAVES][CL_TR], w_jd[CL_WAVES][CL_TR], w_nh[CL_WAVES][CL_TR];
   __shared__ double f_s2[CL_TR], f_d2[CL_TR];
@@ -79,6 +79,7 @@ __global__ void __launch_bounds__(CL_BLOCK) k_clear(ClearArgs A) {
     const int lrow = row0 + tid;
     const int i = lrow < A.nrows ? A.row_begin + lrow * A.row_stride : -1;   // (-1: no such row; nothing is written)
     si[tid] = i;
+    s_on[tid] = i >= 0 && (A.active == nullptr || A.active[i] != 0);
     sp[0][tid] = i >= 0 ? px[i] : 0.0;
     sp[1][tid] = i >= 0 ? py[i] : 0.0;
     sp[2][tid] = i >= 0 ? pz[i] : 0.0;
@@ -91,7 +92,8 @@ __global__ void __launch_bounds__(CL_BLOCK) k_clear(ClearArgs A) {
   for (int r = 0; r < CL_TR; ++r) { bs[r] = inf; bd[r] = inf; js[r] = INT_MAX; jd[r] = INT_MAX; nh[r] = 0; }
   for (int c0 = 0; c0 < ncols; c0 += CL_BLOCK) {
     const int c = c0 + tid;
-    if (c < ncols) {
+    // (an inactive agent is no column; the obstacle columns are not masked)
+    if (c < ncols && (A.active == nullptr || c >= A.n_agents || A.active[c] != 0)) {
       const double cx = px[c], cy = py[c], cz = pz[c], cwxy = pwxy[c], cwz = pwz[c];
 #pragma unroll
       for (int r = 0; r < CL_TR; ++r) {
@@ -140,13 +142,13 @@ __global__ void __launch_bounds__(CL_BLOCK) k_clear(ClearArgs A) {
   // the hit lists: the rows with a hit only, one wave a row
   for (int r = wave; r < CL_TR; r += CL_WAVES) {
     const int i = si[r];
-    if (i < 0 || f_nh[r] == 0) continue;   // (wave-uniform)
+    if (i < 0 || f_nh[r] == 0 || !s_on[r]) continue;   // (wave-uniform)
     const double rx = sp[0][r], ry = sp[1][r], rz = sp[2][r];
     int cnt = 0;
     for (int c0 = 0; c0 < ncols && cnt < 6; c0 += 64) {
       const int c = c0 + lane;
       bool h = false;
-      if (c < ncols && c != i) {
+      if (c < ncols && c != i && (A.active == nullptr || c >= A.n_agents || A.active[c] != 0)) {
         const double dx = rx - px[c], dy = ry - py[c], dz = rz - pz[c];
         const double q = dx * dx + dy * dy;
         const double zz = dz * dz;
@@ -185,6 +187,12 @@ __global__ void __launch_bounds__(CL_BLOCK) k_clear(ClearArgs A) {
     }
     R.fence_min = fm; R.fence_face = ff;
     for (int q = 0; q < 6; ++q) R.hit[q] = f_hit[tid][q];
+    if (!s_on[tid]) {   // not a measured row: the cleared record
+      R.s2_min = R.d2_min = R.fence_min = inf;
+      R.j_s2 = R.j_d2 = R.fence_face = -1;
+      R.n_hit = 0;
+      for (int q = 0; q < 6; ++q) R.hit[q] = -1;
+    }
     A.rows[row0 + tid] = R;
   }
 }

@@ -118,6 +118,14 @@ __global__ void __launch_bounds__(256) k_tables(int X, int U, int H, const doubl
 template <int PS>
 __device__ __forceinline__ void lp_row(const LpArgs& A, int lrow, float* planes, int lane) {
   const int i = A.row_begin + lrow * A.row_stride;
+  if (A.active != nullptr && A.active[i] == 0) {   // not in this step (lqro_set_active): no LP, newV = +0.0
+    if (lane == 0) {
+      A.newv[3 * i] = 0.0;
+      A.newv[3 * i + 1] = 0.0;
+      A.newv[3 * i + 2] = 0.0;
+    }
+    return;
+  }
   int m0 = 0;
   if (A.cap != A.npr) {
     const int nu = A.umax <= 0 ? 0 : A.ucounts ? max(0, min(A.ucounts[i], A.umax)) : A.umax;

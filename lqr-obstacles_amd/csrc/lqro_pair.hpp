@@ -66,7 +66,13 @@ struct PairArgs {
   int hull_cap;
   unsigned long long* stats;          // 8 counters
   unsigned long long* prof;           // LQRO_PAIR_PROFILE: per-phase cycles (16 words)
-  // hot phase (k_prio's list of likely inside-hull pairs; null: none)
+  // hot phase (k_prio's list of likely inside-hull pairs; null: none).
+  // REQUIRED OF EVERY PRODUCER of hot-list, hot-mark or speculative hull-queue
+  // entries: under an activity mask (`active` below) no entry may name a pair
+  // whose row or agent column is inactive.  The hot launches evaluate what
+  // they are given and do not test the mask; today the producers are k_prio
+  // (lists none), k_prio_prev (copies the list k_active has filtered) and
+  // lqro_set_obstacles (empties it)
   const int* hot_list;
   const unsigned char* hot_mark;      // per slot: 1 = in the hot list
   const int* hot_count;
@@ -101,6 +107,14 @@ struct PairArgs {
   // LDS layout, in doubles
   int XP, lds_T, lds_N, lds_S, lds_R, lds_TF, lds_H, lds_wave, wave_doubles;
   int lds_cls, cls_doubles;           // behind lds_H: one block per class with a shape of its own
+  // activity mask (lqro_set_active): k_active's 0 / 1 byte per agent, whole
+  // words; null: everybody takes part.  Read by the row launch alone, in an
+  // instantiation of its own (k_pair<.., kRowLaunch, true>; k_side's and
+  // k_qside's row tails do not sweep under a mask): the hot
+  // lists never hold a pair with an inactive row or column (k_active filters
+  // the carried-over list, k_prio lists none), and with culling the neighbour
+  // lists hold none either (k_nbr)
+  const unsigned char* active;
 };
 
 struct BlockTabs {
@@ -479,7 +493,9 @@ __device__ inline int reach_rank(const PairArgs& P, const WaveTabs& W, int lane,
 
 // One workgroup's share of a k_pair launch (LDS at `lds`, laid out per
 // PairArgs; waves = blockDim.x / 64 <= P.waves).  Also the tail of k_side.
-template <int X, bool RECS, int HOT>
+// MASK: the row launch under an activity mask (lqro_set_active); without it
+// the loops below are the ones a context without a mask always ran.
+template <int X, bool RECS, int HOT, bool MASK = false>
 __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
 #ifdef LQRO_PAIR_PROFILE
   unsigned long long pp[16] = {0};
@@ -867,6 +883,31 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
   // waves take the row's pairs one at a time (LDS counter), so uneven pair
   // costs balance inside the row.  Agent i's horizon tables are staged into
   // LDS only when they change (once per workgroup with shared gains).
+  //
+  // A slot whose row or column is inactive (lqro_set_active): no plane, flag
+  // 0 written this step, and the zero record with the pair's ids.  Lane 0
+  // writes inside one `if` that every lane leaves together: the caller's
+  // `continue` must be reached by the whole wave at once.  (A lane that
+  // returned early took the loop's back edge on its own, the pair loop became
+  // a divergent one, and the lanes running ahead read lane 0's jj for ever.)
+  auto skip_slot = [&](const int i, const int lrow, const int jj) {
+    if (lane == 0) {
+      const size_t cs = (size_t)lrow * P.npr + jj;
+      float4* dst = reinterpret_cast<float4*>(P.planes + cs * 8);
+      dst[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+      dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (RECS) {
+        lqro_pair_record rec;
+        memset(&rec, 0, sizeof rec);
+        rec.i = i; rec.j = jj < i ? jj : jj + 1;
+        P.recs[cs] = rec;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();   // (the wave is whole again here)
+  };
+  // (with culling the neighbour lists carry the mask: an inactive row's list
+  // is all -1, no list names an inactive column)
+  const unsigned char* act = MASK && P.nbr_list == nullptr ? P.active : nullptr;
   long staged = -1;
   for (;;) {
     // work unit = (row, part): a row is split into row_split pair ranges
@@ -883,7 +924,10 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
     const int jj_end = (int)((long)(unit % P.row_split + 1) * P.npr / P.row_split);
     const int i = P.row_begin + lrow * P.row_stride;
     const long ag = P.per_agent ? (long)i : 0;
-    if (ag != staged) {
+    // an inactive row's unit writes its slots' zeros and is counted below like
+    // any other (rowpend); it needs no tables
+    const bool row_on = !MASK || act == nullptr || agent_on_u(act, i);
+    if (row_on && ag != staged) {
       const double* Ti = P.T + ag * H * 9;
       const double* Ni = P.NCF + ag * H * 3 * X;
       const double* Ri = P.R + ag * H;
@@ -907,6 +951,12 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
     if (lane == 0) jj = atomicAdd(&s_next, 1);
     jj = __builtin_amdgcn_readlane(jj, 0);
     if (jj >= jj_end) break;
+    if constexpr (MASK) if (act != nullptr) {   // (jj < obs_jj: an agent column, jj-th other agent of row i)
+      if (!row_on || (jj < P.obs_jj && !agent_on_u(act, jj < i ? jj : jj + 1))) {
+        skip_slot(i, lrow, jj);
+        continue;
+      }
+    }
     if (P.hot_mark != nullptr && P.hot_mark[(size_t)lrow * P.npr + jj]) continue;   // done in the hot phase
     do_pair(i, lrow, jj);
   }
@@ -956,10 +1006,10 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
 // without the record code and its registers.  HOT: the hot launch (P.hot_only)
 // and the row launch are separate instantiations, so neither carries the
 // other's loop around do_pair.
-template <int X, bool RECS, int HOT>
+template <int X, bool RECS, int HOT, bool MASK = false>
 __global__ void __launch_bounds__(LQRO_PAIR_LB) k_pair(PairArgs P) {
   extern __shared__ double lds[];
-  pair_block<X, RECS, HOT>(P, lds);
+  pair_block<X, RECS, HOT, MASK>(P, lds);
 }
 
 #ifndef LQRO_PAIR_TU   // the non-template kernels: defined once, in lqro_runtime.hip
@@ -972,18 +1022,24 @@ __global__ void __launch_bounds__(LQRO_PAIR_LB) k_pair(PairArgs P) {
 // and counts the kept pairs into LQRO_ST_PAIRS.
 __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int row_begin, int row_stride, int npr,
                                             double r2,
-                                            int k, int K, int* list, unsigned long long* stats) {
+                                            int k, int K, int* list, unsigned long long* stats,
+                                            const unsigned char* act, int n_agents) {
   constexpr int kCap = 1024;   // candidates within r held in LDS
   __shared__ double cd[kCap];
   __shared__ int cj[kCap];
   const int lrow = blockIdx.x, lane = threadIdx.x, i = row_begin + lrow * row_stride;
+  // the activity mask (lqro_set_active; null: none): an inactive agent is no
+  // candidate, an inactive row has none (its list is all -1); obstacle
+  // columns (j >= n_agents) are not masked
+  const bool row_on = act == nullptr || act[i] != 0;
+  auto on = [&](int j) { return act == nullptr || (row_on && (j >= n_agents || act[j] != 0)); };
   const double* xi = x + (size_t)i * X;
   // one scan: the agents within r (ascending j), usually a few dozen
   int ncand = 0;
   for (int base = 0; base < N; base += 64) {
     const int j = base + lane;
     double d2 = INFINITY;
-    if (j < N && j != i) {
+    if (j < N && j != i && on(j)) {
       const double* xj = x + (size_t)j * X;
       const double dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
       d2 = dx * dx + dy * dy + dz * dz;
@@ -1010,7 +1066,7 @@ __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int r
       }
     } else {
       for (int j = lane; j < N; j += 64) {
-        if (j == i) continue;
+        if (j == i || !on(j)) continue;
         const double* xj = x + (size_t)j * X;
         const double dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
         const double d2 = dx * dx + dy * dy + dz * dz;
@@ -1049,7 +1105,7 @@ __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int r
   for (int base = 0; base < npr; base += 64) {
     const int jj = base + lane;
     bool sel = false;
-    if (jj < npr && taken > 0) {
+    if (jj < npr && taken > 0 && on(jj < i ? jj : jj + 1)) {
       const int j = jj < i ? jj : jj + 1;
       const double* xj = x + (size_t)j * X;
       const double dx = xi[0] - xj[0], dy = xi[1] - xj[1], dz = xi[2] - xj[2];
@@ -1062,6 +1118,69 @@ __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int r
   }
   for (int q = cnt + lane; q < K; q += 64) row[q] = -1;
   if (lane == 0) atomicAdd(&stats[LQRO_ST_PAIRS], (unsigned long long)taken);
+}
+
+// k_active: the activity mask at the head of a step (lqro_set_active; one
+// workgroup, launched only with a mask set).  The caller's bytes (the device
+// form's may change between steps) become the 0 / 1 bytes the step's kernels
+// read, whole words; the pairs statistic, the slots the sweep visits: for each
+// active own row the active agents other than itself plus the n_obs obstacle
+// columns (pairs null with culling: k_nbr counts the kept ones); and the
+// last step's inside-hull list (k_prio_save's, null: none) loses the pairs
+// whose row or agent column is inactive now, in place and in order, before
+// k_prio_prev lists, marks or queues one: what it carries into the hot list,
+// the side stream's first hot launch and the speculative hull queue is active.
+// An inactive own row's newV is the LP launch's (lp_row writes +0.0).
+struct ActiveArgs {
+  const unsigned char* src;   // n_agents bytes, the caller's
+  unsigned char* act;         // (n_agents + 3) & ~3 bytes
+  int n_agents, n_obs, npr;
+  int nrows, row_begin, row_stride;
+  unsigned long long* pairs;
+  int* prev;
+  int* prevn;
+  int cap;
+};
+
+__global__ void __launch_bounds__(256) k_active(ActiveArgs A) {
+  __shared__ int n_on, n_rows_on;
+  if (threadIdx.x == 0) { n_on = 0; n_rows_on = 0; }
+  __syncthreads();
+  const int npad = (A.n_agents + 3) & ~3;
+  int mine = 0, rows = 0;
+  for (int q = threadIdx.x; q < npad; q += blockDim.x) {
+    const bool on = q < A.n_agents && A.src[q] != 0;
+    A.act[q] = on ? 1 : 0;
+    mine += on ? 1 : 0;
+    const int d = q - A.row_begin;   // an own row: row_begin + r row_stride, r < nrows
+    if (on && d >= 0 && d % A.row_stride == 0 && d / A.row_stride < A.nrows) ++rows;
+  }
+  if (mine) atomicAdd(&n_on, mine);
+  if (rows) atomicAdd(&n_rows_on, rows);
+  __syncthreads();
+  if (threadIdx.x == 0 && A.pairs != nullptr)
+    *A.pairs = (unsigned long long)n_rows_on * (unsigned long long)(max(n_on - 1, 0) + A.n_obs);
+  if (A.prev == nullptr || threadIdx.x >= 64) return;
+  // one wave, 64 entries a pass: a pass is read before it is written, and
+  // nothing is written ahead of what was read
+  const int lane = threadIdx.x;
+  const long total = (long)A.nrows * A.npr;
+  const int m = min(*A.prevn, A.cap);
+  int kept = 0;
+  for (int base = 0; base < m; base += 64) {
+    const int q = base + lane;
+    const int slot = q < m ? A.prev[q] : -1;
+    bool keep = slot >= 0 && slot < total;
+    if (keep) {
+      const int lrow = slot / A.npr, jj = slot - lrow * A.npr;
+      const int i = A.row_begin + lrow * A.row_stride, j = jj < i ? jj : jj + 1;
+      keep = A.src[i] != 0 && (j >= A.n_agents || A.src[j] != 0);
+    }
+    const unsigned long long bal = __ballot(keep);
+    if (keep) A.prev[kept + __popcll(bal & ((1ull << lane) - 1ull))] = slot;
+    kept += __popcll(bal);
+  }
+  if (lane == 0) *A.prevn = kept;
 }
 
 // k_prio: which pairs go first.  A pair whose relative motion brings the two
@@ -1095,6 +1214,10 @@ struct PrioArgs {
   int* hcount;
   int hq_cap;
   int* spec_n;   // (the speculative entries' count, for hull_take_job)
+  // activity mask (lqro_set_active; null: none, k_prio<false>): a pair whose row
+  // or agent column (j < n_agents) is inactive is never listed, marked or queued
+  const unsigned char* act;
+  int n_agents;
 };
 
 // the last step's inside-hull pairs at the head of the hot list (one block)
@@ -1188,6 +1311,9 @@ __global__ void __launch_bounds__(256) k_prio_save(const int* hq, const int* hco
   if (threadIdx.x == 0) *prevn = m;
 }
 
+// (MASK: under an activity mask; without it the kernel is the one a context
+// without a mask always ran, on the step's critical path ahead of the sweep)
+template <bool MASK>
 __global__ void __launch_bounds__(256) k_prio(PrioArgs A) {
   const long total = (long)A.nrows * A.npr;
   const int lane = threadIdx.x & 63;
@@ -1207,6 +1333,7 @@ __global__ void __launch_bounds__(256) k_prio(PrioArgs A) {
       t = fmin(fmax(t, 0.0), A.t_hot);
       const double e0 = p0 + t * v0, e1 = p1 + t * v1, e2 = p2 + t * v2;
       hot = e0 * e0 + e1 * e1 + e2 * e2 <= A.r2_hot;
+      if constexpr (MASK) hot = hot && A.act[i] != 0 && (j >= A.n_agents || A.act[j] != 0);
     }
     const unsigned long long b = __ballot(hot);
     int pos = 0;

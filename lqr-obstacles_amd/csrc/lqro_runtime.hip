@@ -431,6 +431,40 @@ int lqro_set_fence(lqro_ctx* c, const double* lo, const double* hi, double tau) 
   return LQRO_OK;
 }
 
+// lqro_set_active[_device].  own: `active` is a host array to copy.
+static int set_active(lqro_ctx* c, const uint8_t* active, bool own) {
+  if (!c) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;   // the pending half-step's tail was enqueued under the old mask
+  if (int rc = ctx_enter(c, false)) return rc;
+  if (!active) {   // the context that never had a mask: no buffer, no launch
+    c->mem.release(c->d_actown);
+    c->mem.release(c->d_act);
+    c->d_actsrc = nullptr;
+    return LQRO_OK;
+  }
+  const size_t N = (size_t)c->cfg.n_agents;
+  // every new buffer first: a failed call leaves the context as it was
+  unsigned char *copy = nullptr, *act = nullptr;
+  int rc = LQRO_OK;
+  if (!c->d_act && c->mem.get(act, (N + 3) & ~(size_t)3)) rc = LQRO_E_NOMEM;
+  if (!rc && own && c->mem.get(copy, N)) rc = LQRO_E_NOMEM;
+  // (the stream the step reads them on may be non-blocking: the copy is synchronous)
+  if (!rc && own && hipMemcpy(copy, active, N, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  if (rc) {
+    c->mem.release(act); c->mem.release(copy);
+    return rc;
+  }
+  if (act) c->d_act = act;
+  c->mem.release(c->d_actown);
+  c->d_actown = copy;
+  c->d_actsrc = own ? copy : active;
+  return LQRO_OK;
+}
+
+int lqro_set_active(lqro_ctx* c, const uint8_t* active) { return set_active(c, active, true); }
+
+int lqro_set_active_device(lqro_ctx* c, const uint8_t* d_active) { return set_active(c, d_active, false); }
+
 int lqro_set_hard_planes(lqro_ctx* c, int32_t level) {
   if (!c || level < LQRO_HARD_NONE || level > LQRO_HARD_OBSTACLES) return LQRO_E_ARG;
   if (c->pending) return LQRO_E_STATE;   // the pending half-step's LP was planned with the old level
@@ -638,6 +672,7 @@ static LpArgs lp_args(const lqro_ctx* c, int npr, const double* d_vgoal, double*
   La.hard = c->hard_level;
   La.obs_first = c->hard_level >= LQRO_HARD_OBSTACLES && c->nobs > 0 ? c->cfg.n_agents - 1 : -1;
   La.nbr = c->nbr_k > 0 ? c->d_nbrlist : nullptr;
+  La.active = c->d_actsrc ? c->d_act : nullptr;   // (k_active's bytes, written at the head of the step)
   return La;
 }
 
@@ -692,6 +727,7 @@ static PairArgs pair_args(const lqro_ctx* c, const StepPlan& plan, const double*
   P.qnrm = c->qhull_order ? c->d_qnrm : nullptr;
   P.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;   // (k_nbr fills it)
   P.rowpend = plan.early ? c->d_rowpend : nullptr;
+  P.active = c->d_actsrc ? c->d_act : nullptr;
   if (plan.hot) {
     P.hot_list = c->d_hotlist; P.hot_mark = c->d_hotmark; P.hot_count = c->d_hcount + LQRO_HC_HOT;
     P.hot_next = c->d_hcount + LQRO_HC_HOT_NEXT; P.hot_cap = c->hot_cap;
@@ -722,6 +758,7 @@ static PrioArgs prio_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
   Q.t_hot = c->knobs.hot_t; Q.r2_hot = c->knobs.hot_r * c->knobs.hot_r;   // seconds, metres (scheduling heuristic)
   Q.list = c->d_hotlist; Q.mark = c->d_hotmark; Q.count = c->d_hcount + LQRO_HC_HOT; Q.cap = c->hot_cap;
   Q.rowpend = P.rowpend;
+  Q.act = P.active; Q.n_agents = c->cfg.n_agents;
   if (plan.split) {
     Q.prev = c->d_prevq; Q.prevn = c->d_hot2 + LQRO_H2_PREV; Q.hot1n = c->d_hot2 + LQRO_H2_HOT1;
     Q.hot2next = c->d_hot2 + LQRO_H2_HOT2_NEXT;
@@ -813,6 +850,7 @@ static int enqueue_clear(lqro_ctx* c, const double* d_x, lqro_clearance_row* row
     A.lo[q] = c->fence_lo[q]; A.hi[q] = c->fence_hi[q]; A.m[q] = q < 2 ? g.xy_radius : g.z_radius;
   }
   A.rows = rows; A.tot = c->d_cltot;
+  A.active = c->d_actsrc;   // (the caller's bytes: an explicit measurement runs without a step)
   LAUNCH(launch_clear(s, A, ev));
   HIPCHK(hipEventRecord(c->cev, s));
   c->measured = 1;
@@ -838,9 +876,19 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
   // Qhull order: the normal the last step's last eligible pair left enters this step
   if (c->qhull_order)
     HIPCHK(hipMemcpyAsync(c->d_carry, c->d_carry + 3, sizeof(double) * 3, hipMemcpyDeviceToDevice, s));
+  // the activity mask: this step's bytes, its pairs counter, the carried-over list without the pairs that left
+  if (c->d_actsrc) {
+    ActiveArgs Aa{};
+    Aa.src = c->d_actsrc; Aa.act = c->d_act;
+    Aa.n_agents = g.n_agents; Aa.n_obs = c->nobs; Aa.npr = c->npr;
+    Aa.nrows = c->nrows; Aa.row_begin = c->rb; Aa.row_stride = c->rs;
+    Aa.pairs = c->nbr_k > 0 ? nullptr : c->d_stats + LQRO_ST_PAIRS;
+    if (c->qhull_order) { Aa.prev = c->d_prevq; Aa.prevn = c->d_hot2 + LQRO_H2_PREV; Aa.cap = c->hot_cap; }
+    LAUNCH(hipLaunchKernelGGL(k_active, dim3(1), dim3(256), 0, s, Aa));
+  }
   if (c->nbr_k > 0) {
     LAUNCH(hipLaunchKernelGGL(k_nbr, dim3((unsigned)c->nrows), dim3(64), 0, s, P.x, g.x_dim, g.n_agents + c->nobs, c->rb, c->rs,
-                              c->npr, c->nbr_r2, c->nbr_k, plan.npr, c->d_nbrlist, c->d_stats));
+                              c->npr, c->nbr_r2, c->nbr_k, plan.npr, c->d_nbrlist, c->d_stats, P.active, g.n_agents));
   }
   if (plan.early) HIPCHK(hipMemsetAsync(c->d_rowpend, 0, sizeof(int) * 2 * (size_t)c->nrows, s));
   if (c->nfence > 0) {   // this step's fence planes, before any LP can start
@@ -863,7 +911,8 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
       LAUNCH(hipLaunchKernelGGL(k_prio_prev, dim3(1), dim3(256), 0, s, Q));
     }
     const long nb = std::min<long>((plan.slots + 255) / 256, 8L * c->n_cu);
-    LAUNCH(hipLaunchKernelGGL(k_prio, dim3((unsigned)nb), dim3(256), 0, s, Q));
+    if (Q.act) LAUNCH(hipLaunchKernelGGL(k_prio<true>, dim3((unsigned)nb), dim3(256), 0, s, Q));
+    else LAUNCH(hipLaunchKernelGGL(k_prio<false>, dim3((unsigned)nb), dim3(256), 0, s, Q));
   }
   return LQRO_OK;
 }
@@ -882,7 +931,7 @@ static int enqueue_side(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, co
     if (plan.qside) {
       PairArgs Pq = P;
       Pq.max_waves = plan.qside_waves;
-      if (plan.nside == 0) Pq.nrows = 0;
+      if (plan.nside == 0 || P.active) Pq.nrows = 0;   // (under a mask the main stream's row launch sweeps every row)
       LAUNCH(launch_qside(x_dim, dim3(std::min(nwait, c->qworkers)), c->side, Hh, Pq));
     } else {
       if (!c->knobs.qhull_big) {
@@ -906,7 +955,7 @@ static int enqueue_side(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, co
   } else {
     PairArgs Pt = P;
     Pt.max_waves = plan.side_waves;
-    if (plan.nside == 0) Pt.nrows = 0;
+    if (plan.nside == 0 || P.active) Pt.nrows = 0;   // (as k_qside's tail)
     LAUNCH(launch_side(x_dim, dim3(nwait), dim3(HULL_CTHREADS), c->side, Hh, Pt));
   }
   return LQRO_OK;
@@ -1033,6 +1082,7 @@ static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   double* d_lpnv = d_newv != nullptr ? d_newv : (phase == 1 ? c->d_newv : nullptr);   // the early LP's newV
   const StepPlan plan = plan_step(step_shape(c, phase, d_lpnv, d_newv), c->knobs, fb, fb.inside != ~0ull);
   c->early_step = plan.early ? 1 : 0;
+  c->act_step = c->d_actsrc ? 1 : 0;
   c->early_internal = plan.early_internal ? 1 : 0;
   // 2. the kernels' arguments
   const PairArgs P = pair_args(c, plan, c->nobs > 0 ? c->d_cols : d_x);   // (k_cols fills d_cols in the prologue)
@@ -1374,7 +1424,8 @@ int lqro_get_stats_ex(lqro_ctx* c, int64_t* st, int32_t n) {
   if (int rc = ctx_enter(c, true)) return rc;   // (pending: the half-step's counters are not final)
   unsigned long long h[LQRO_ST_FAILS];
   HIPCHK(hipMemcpy(h, c->d_stats, sizeof h, hipMemcpyDeviceToHost));
-  if (c->nbr_k <= 0) h[LQRO_ST_PAIRS] = (unsigned long long)c->nrows * c->npr;   // else k_nbr counted the kept pairs
+  // (with culling k_nbr counted the kept pairs, under a mask k_active the slots visited)
+  if (c->nbr_k <= 0 && !c->act_step) h[LQRO_ST_PAIRS] = (unsigned long long)c->nrows * c->npr;
   // [0..10] the device words; [11] LQRO_REC_QHMERGE_WIN pairs (device word
   // LQRO_ST_MWIN; word 11 counts the failures lqro_get_hull_failures names)
   for (int k = 0; k < n; ++k)

@@ -208,6 +208,7 @@ EXPORTS = (
     "lqro_clearance", "lqro_clearance_device", "lqro_set_monitor", "lqro_get_monitor",
     "lqro_get_monitor_rows", "lqro_get_monitor_pairs",
     "lqro_set_lp_audit", "lqro_get_lp_audit", "lqro_get_lp_audit_rows", "lqro_audit_new_v",
+    "lqro_set_active", "lqro_set_active_device",
 )
 # lqro_set_hard_planes' levels: the planes linearProgram4 does not relax
 LQRO_HARD_NONE, LQRO_HARD_FENCE, LQRO_HARD_HEAD, LQRO_HARD_OBSTACLES = 0, 1, 2, 3
@@ -285,6 +286,9 @@ def lib() -> C.CDLL:
             L.lqro_get_lp_audit.argtypes = [vp, C.POINTER(LpTotal), C.POINTER(LpTotal), i32]
             L.lqro_get_lp_audit_rows.argtypes = [vp, vp, i64, C.POINTER(i64)]
             L.lqro_audit_new_v.argtypes = [vp, vp, vp, i32, vp, vp, C.c_float, vp, C.POINTER(LpTotal), i32]
+        if hasattr(L, "lqro_set_active"):   # (older libraries in A/B runs lack them)
+            L.lqro_set_active.argtypes = [vp, vp]
+            L.lqro_set_active_device.argtypes = [vp, vp]
         L.lqro_set_carry_normal.argtypes = [vp, vp]
         L.lqro_get_carry_normal.argtypes = [vp, vp]
         _lib = L
@@ -418,6 +422,7 @@ class Context:
         self.row_ids = np.arange(rb, re, max(cfg.row_stride, 1))   # the agents whose rows this computes
         self.n_obstacles = 0
         self._obs_keep = None      # a device tensor given to set_obstacles, kept alive
+        self._act_keep = None      # ... and one given to set_active
 
     def close(self):
         if self._h:
@@ -521,6 +526,40 @@ class Context:
             name = "lqro_set_obstacles_device" if dev else "lqro_set_obstacles"
             _check(getattr(lib(), name)(self._h, ptr, m, oxy, oz, resp), name)
         self.n_obstacles, self._obs_keep = m, (states if dev and m else None)
+
+    def set_active(self, mask):
+        """Which agents take part in the steps that follow (lqro_set_active):
+        an inactive agent is neither a row nor a column, the step equals the
+        step over the compacted swarm, and its own row's newV is +0.0.  mask:
+        a numpy bool / uint8 array of n_agents entries (copied; another length
+        raises ValueError), or a uint8 torch tensor of n_agents bytes on the
+        context's device, or an integer device pointer to as many, read when
+        each step runs (rewrite it on the step's stream before the step; the
+        tensor is kept alive here).  None clears: everybody takes part."""
+        n = self.cfg.n_agents
+        if mask is None:
+            _check(lib().lqro_set_active(self._h, None), "lqro_set_active")
+            self._act_keep = None
+            return
+        if isinstance(mask, (int, np.integer)) and not isinstance(mask, (bool, np.bool_)):
+            _check(lib().lqro_set_active_device(self._h, C.c_void_p(int(mask))), "lqro_set_active_device")
+            self._act_keep = None
+            return
+        if hasattr(mask, "data_ptr"):
+            import torch
+            if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or mask.numel() != n:
+                raise ValueError(f"set_active: need a contiguous uint8 device tensor of {n} bytes")
+            _check(lib().lqro_set_active_device(self._h, C.c_void_p(mask.data_ptr())), "lqro_set_active_device")
+            self._act_keep = mask
+            return
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ and m.dtype != np.uint8:
+            raise ValueError("set_active: a bool or uint8 array")
+        if m.ndim != 1 or m.shape[0] != n:
+            raise ValueError(f"set_active: {m.shape} entries for {n} agents")
+        m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+        _check(lib().lqro_set_active(self._h, _p(m)), "lqro_set_active")
+        self._act_keep = None
 
     def set_hard_planes(self, level: int):
         """Which planes linearProgram4 keeps out of its relaxation
@@ -1026,6 +1065,12 @@ class Simulator:
         (Context.set_hard_planes)."""
         self.ctx.set_hard_planes(level)
 
+    def set_active(self, mask):
+        """Which quadrotors of qlist take part in step() (Context.set_active;
+        None: all).  An inactive one is avoided by nobody and step() leaves its
+        newV at zero; update() goes on propagating every agent."""
+        self.ctx.set_active(mask)
+
     def clearance(self):
         """Context.clearance on the agents' current estimates q.x."""
         return self.ctx.clearance(np.stack([q.x for q in self.qlist]))
@@ -1269,6 +1314,12 @@ class DeviceLoop:
         """This rank's context takes the hardness level (every rank the same;
         Context.set_hard_planes)."""
         self.ctx.set_hard_planes(level)
+
+    def set_active(self, mask):
+        """This rank's context takes the activity mask (every rank the same
+        global array; Context.set_active).  It governs step() alone: update()
+        goes on propagating every own agent."""
+        self.ctx.set_active(mask)
 
     def monitor(self, reset: bool = False):
         """This rank's (last, since_reset) clearance totals (Context.monitor);
