@@ -87,6 +87,9 @@ typedef struct lqro_config {
   int32_t min_reach;     /* pairs with n_reach <= min_reach emit no plane (4, LQRO:1409) */
   double  xy_radius;     /* XYRADIUS (LQRO:13); the sphere uses 2*XYRADIUS        */
   double  z_radius;      /* ZRADIUS  (LQRO:14)                                    */
+                         /* a zero semi-axis (a flat set, a needle, a point) is
+                          * accepted by the step and refused by the clearance
+                          * calls (LQRO_E_ARG, see lqro_clearance)              */
   double  vmax_reach;    /* reachable-velocity radius, 30 (LQRO:1387)             */
   double  vmax_lp;       /* LP speed bound, 100 (LQRO:1224)                        */
   int32_t row_begin;     /* agents [row_begin,row_end) are this context's rows    */

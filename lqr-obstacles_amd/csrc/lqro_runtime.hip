@@ -225,12 +225,18 @@ static bool pair_set_lds(int lds_bytes) {
 }
 
 // max |u_p| with s_p = diag(rad) u_p (createSpheres, :743-745), with the
-// bound's margin
+// bound's margin.  A zero semi-axis contributes nothing: every point's
+// coordinate on it is 0, so its u is 0 (0 / 0 would make u2 a NaN that
+// std::max drops, and the whole set's bound 0)
 static double sphere_umax(const double* S, int NP, const double* rad) {
   double um = 0.0;
   for (int p = 0; p < NP; ++p) {
     double u2 = 0.0;
-    for (int d = 0; d < 3; ++d) { const double u = S[3 * p + d] / rad[d]; u2 += u * u; }
+    for (int d = 0; d < 3; ++d) {
+      if (rad[d] == 0.0) continue;
+      const double u = S[3 * p + d] / rad[d];
+      u2 += u * u;
+    }
     um = std::max(um, std::sqrt(u2));
   }
   return um * (1.0 + 1e-12);
