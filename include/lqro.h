@@ -673,6 +673,99 @@ int lqro_get_monitor_rows(lqro_ctx* ctx, lqro_clearance_row* rows, int64_t capac
  * the total's n_hit. */
 int lqro_get_monitor_pairs(lqro_ctx* ctx, int64_t* pairs /* 2 per pair */, int64_t capacity, int64_t* n_out);
 
+/* ---- horizon conflict prediction: each row's first predicted collision ----
+ * An opt-in measurement, on the device: with the velocities v the step chose
+ * (or any other N x 3 array), does the closed loop the LQR-obstacle was built
+ * from keep each pair apart over the horizon, and if not, when and with whom
+ * does it first fail?  The reference has no counterpart.  All fp64, every
+ * operation rounded once, sums taken in ascending index order starting from
+ * 0.0; no division and no sqrt on the device.
+ * Tables.  For each gains set g (one, or N with per-agent gains) the step's
+ * own recursion in its order: At = A + (B L), Bt = B E, G <- 0, then H times
+ *   G <- (sum_m At[r][m] G[m][c]) + Bt[r][c];
+ * CG_k is rows 0..2 of G after update k + 1, k = 0 .. H-1: slice k is the
+ * state k + 1 steps ahead, the index of the step's T_k and NCF_k = -C F_k.
+ * Path of a body b under set g with commanded velocity v_b, r = 0..2:
+ *   P_b,k[r] = (sum_{c<3} CG_k[r][c] v_b[c]) - (sum_{m<X} NCF_k[r][m] x_b[m]).
+ * An agent is predicted with its OWN set (with shared gains this equals the
+ * step's model C F_k (x_i - x_j) + C G_k (v_i - v_j) in exact arithmetic).  An
+ * obstacle has no gains: in row i it is predicted with ROW i's tables and
+ * v_o = x_o[3..5], as the step treats it.  The affine terms c and l of the
+ * closed loop are left out, as the method leaves them out.
+ * Pair (own row i, column c, slice k).  Columns are the agents c != i, then
+ * the obstacle columns n_agents + o, as in lqro_clearance.  With
+ * d = P_i,k - P_c,k per component:
+ *   q = dx dx + dy dy;  d2 = q + dz dz;  s2 = q wxy_c + (dz dz) wz_c
+ * with lqro_clearance's host-formed weights over the summed radii; a HIT is
+ * s2 < 1.0, strictly.  Self is skipped by index.  lqro_set_neighbors does not
+ * apply.  With lqro_set_active (the caller's bytes, read when the measurement
+ * runs) an inactive agent is neither a row nor a column; its row gets the
+ * cleared record.  Obstacle columns are never masked.  Inputs must be finite.
+ * Deterministic by construction: (value, index) keys, integer counts, no
+ * floating-point atomics, no dependence on tile size, wave count or
+ * schedule; a numpy restatement (tests/predict_ref.py) matches bit for bit.
+ * Indices are -1 and minima +inf where nothing was measured. */
+#define LQRO_PREDICT_TILE 8   /* own rows a workgroup of the pair kernel (no part of the result) */
+typedef struct lqro_predict_row {
+  double s2_min, d2_min;    /* over the columns and slices                               */
+  int32_t j_s2, k_s2;       /* column and slice of s2_min: the smallest (value, column, slice) wins */
+  int32_t j_d2, k_d2;       /* of d2_min, same rule                                      */
+  int32_t k_first, j_first; /* the smallest slice with a hit; the smallest column hit at that slice */
+  int32_t n_conf;           /* columns with a hit at any slice: the true count           */
+  int32_t reserved;         /* 0                                                         */
+  int32_t conf[4];          /* the first four conflict columns, ascending, -1 padded     */
+} lqro_predict_row;
+
+/* Over a context's own rows.  s2 / d2: the smallest (value, i, j, k) wins;
+ * first: the smallest (k, i, j).  n_conf counts ordered (row, column) pairs. */
+typedef struct lqro_predict_total {
+  double s2_min, d2_min;
+  int32_t s2_i, s2_j, s2_k, d2_i, d2_j, d2_k;
+  int32_t first_k, first_i, first_j, reserved;
+  int64_t n_conf;           /* sum of the rows' n_conf                                   */
+  int64_t n_rows_conf;      /* rows with n_conf > 0                                      */
+  int64_t n_measured;       /* measurements folded in (1 for a last total)               */
+} lqro_predict_total;
+#ifdef __cplusplus
+static_assert(sizeof(lqro_predict_row) == 64, "lqro_predict_row is 64 bytes");
+static_assert(sizeof(lqro_predict_total) == 80, "lqro_predict_total is 80 bytes");
+#endif
+
+/* The context keeps two totals on the device, LAST and SINCE RESET (minima
+ * of minima, sums of counts; a strictly smaller value replaces the kept one,
+ * so the indices are those of the earliest measurement attaining it).  A row
+ * shard measures its own rows against all columns; the caller merges the
+ * ranks' totals (lqro.py merge_prediction; lqro::ShardedSimulator does not).
+ * There is no hook inside lqro_step: a row shard does not hold the other
+ * rows' newV, so the hosts call these entry points.  Errors: LQRO_E_ARG for
+ * NULL inputs and radii that are not positive and finite; LQRO_E_STATE while
+ * a lqro_step_device_begin is pending and, for lqro_predict[_device], before
+ * lqro_set_gains.  Buffers come from the context's pool at the first call
+ * that needs them, after the last step and never inside one; lqro_set_gains
+ * only marks the CG table stale (the next predicting call rebuilds it);
+ * lqro_set_obstacles* resizes the buffers before its swap. */
+
+/* Predicts from the host arrays x (N x X) and v (N x 3) and waits.  rows: the
+ * context's own rows in row order (NULL: not wanted); total: this
+ * measurement's (NULL: not wanted). */
+int lqro_predict(lqro_ctx* ctx, const double* x, const double* v, lqro_predict_row* rows, lqro_predict_total* total);
+/* The same on device arrays, asynchronous on the caller's stream, ordered
+ * behind the context's last step and last measurement by event waits; once
+ * the buffers exist it never waits on the host.  d_rows NULL: the context's
+ * own row buffer (lqro_clearance_device's rules). */
+int lqro_predict_device(lqro_ctx* ctx, const double* d_x, const double* d_v, lqro_predict_row* d_rows, void* stream);
+/* The same measurement over caller-given paths [(N + M)][H][3] (an external
+ * planner's trajectories): the M obstacle columns are the caller's own and
+ * are treated as plain columns with the obstacle columns' weights. */
+int lqro_predict_paths(lqro_ctx* ctx, const double* paths, lqro_predict_row* rows, lqro_predict_total* total);
+int lqro_predict_paths_device(lqro_ctx* ctx, const double* d_paths, lqro_predict_row* d_rows, void* stream);
+/* As lqro_get_monitor and lqro_get_monitor_rows. */
+int lqro_get_prediction(lqro_ctx* ctx, lqro_predict_total* last, lqro_predict_total* since_reset, int32_t reset);
+int lqro_get_prediction_rows(lqro_ctx* ctx, lqro_predict_row* rows, int64_t capacity, int64_t* n_out);
+/* The agents' paths of the last lqro_predict[_device] as [agent][k][3];
+ * LQRO_E_STATE when the last measurement used given paths or there is none. */
+int lqro_get_paths(lqro_ctx* ctx, double* out /* N*H*3 */);
+
 /* ---- LP audit: what did the LP do with each row's planes? ---------------
  * An opt-in measurement, on the device, of the step's result against the
  * plane list each own row's LP saw.  The reference has no counterpart.  For

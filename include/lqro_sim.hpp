@@ -215,6 +215,24 @@ class Simulator {
     return last;
   }
 
+  // Horizon conflict prediction (lqro_predict): with every agent's current
+  // estimate Quadrotor::x and the velocity newV the last step() chose, does
+  // the closed loop keep each pair apart over the horizon, and if not, when
+  // and with whom does it first fail?  rows, when given, receives one record
+  // per agent.  Returns this prediction's total.  (lqro::ShardedSimulator has
+  // no counterpart: a rank predicts with its own context, the caller merges.)
+  lqro_predict_total predict(std::vector<lqro_predict_row>* rows = nullptr) {
+    std::vector<double> v(q_.size() * kV);
+    for (size_t i = 0; i < q_.size(); ++i) {
+      for (int c = 0; c < kX; ++c) xs_[i * kX + c] = q_[i].x[c];
+      for (int c = 0; c < kV; ++c) v[i * kV + c] = q_[i].newV[c];
+    }
+    if (rows) rows->resize(q_.size());
+    lqro_predict_total t;
+    check(lqro_predict(ctx_, xs_.data(), v.data(), rows ? rows->data() : nullptr, &t), "lqro_predict");
+    return t;
+  }
+
   // The LP audit (lqro_set_lp_audit): with on, every step() measures its
   // result against each plane the agent's LP saw, on the device; tol >= 0 is
   // the margin above which a plane counts as violated.  lp_audit() returns

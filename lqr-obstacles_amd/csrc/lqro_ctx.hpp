@@ -121,6 +121,19 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   lqro_clearance_row* d_clrows;   // nrows: the context's own row buffer
   const lqro_clearance_row* cl_last;   // the last measurement's rows: d_clrows or the caller's
   lqro_clearance_total* d_cltot;  // [0] last, [1] since reset
+  // horizon conflict prediction (lqro_predict[_device], lqro_predict_paths[_device]):
+  // allocated by the first call that needs them, never in a step; its
+  // measurements share `measured` / `cev` with the clearance calls
+  double* d_pcg;                  // gains sets x H x 9: C G_k (k_pred_cg)
+  int pcg_sets;                   // the sets d_pcg is allocated for
+  int pcg_stale;                  // lqro_set_gains ran since d_pcg was built
+  double* d_ppath;                // [H][3][n_agents + nobs]: the bodies' paths
+  double* d_pv;                   // n_agents x 3: lqro_predict's copy of v
+  double* d_pgiven;               // (n_agents + nobs) x H x 3: lqro_predict_paths' copy
+  lqro_predict_row* d_prrows;     // nrows: the context's own row buffer
+  const lqro_predict_row* pr_last;   // the last prediction's rows: d_prrows or the caller's
+  lqro_predict_total* d_prtot;    // [0] last, [1] since reset
+  int pr_kind;                    // the last prediction: 0 none, 1 predicted paths, 2 given paths
   // LP audit (lqro_set_lp_audit): allocated by the call that turns it on, never in a step
   int lp_audit;                   // every step audits its own rows at the end of its tail
   float audit_tol;

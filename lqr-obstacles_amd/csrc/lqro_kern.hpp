@@ -106,7 +106,40 @@ struct LpAuditArgs {
   lqro_lp_total* tot;    // [0] last, [1] since reset
 };
 
+// The horizon conflict prediction (lqro_predict[_device],
+// lqro_predict_paths[_device]; lqro_kern_predict.hip): own rows against every
+// column at every slice, lqro.h's contract.  path: the bodies' paths as a
+// structure of arrays [H][3][nc], nc = n_agents + nobs.
+struct PredArgs {
+  int n_agents, nobs, X, U, H;
+  int nrows, row_begin, row_stride;
+  int nsets;            // gains sets: 1, or n_agents
+  int ncols;            // the columns k_conf streams: n_agents (the predicting calls: k_conf_obs takes the
+                        // obstacles), n_agents + nobs (given paths)
+  int nc;               // the path array's pitch, n_agents + nobs
+  const double *A, *B, *L, *E;   // the gains (k_pred_cg)
+  const double* NCF;    // k_tables': nsets x H x 3 x X
+  double* cg;           // nsets x H x 9: C G_k
+  const double* x;      // n_agents x X
+  const double* v;      // n_agents x 3: the commanded velocities
+  const double* obs;    // nobs x X: the obstacles' states as the step reads them
+  const double* ow;     // nobs x 2: the obstacle columns' wxy, wz
+  double wxy, wz;       // the agent columns' weights
+  const double* given;  // null, or the caller's paths [(n_agents + nobs)][H][3]
+  double* path;
+  lqro_predict_row* rows;     // nrows records, the own rows in row order
+  lqro_predict_total* tot;    // [0] last, [1] since reset
+  const unsigned char* active;   // as ClearArgs::active
+};
+
 namespace lqro {
+// k_pred_cg: the C G_k table of every gains set
+void launch_predict_cg(hipStream_t s, const PredArgs& P);
+// k_pred_paths or k_pred_tr, k_conf, k_conf_obs, k_conf_total: one measurement
+// (ev: five timing events recorded around the four launches, scripts/predict_bench.py; else null)
+void launch_predict(hipStream_t s, const PredArgs& P, hipEvent_t* ev = nullptr);
+// k_conf's dynamic LDS: the tile's rows' paths
+size_t predict_lds_bytes(int H);
 // k_clear_pack, k_clear, k_clear_total: one measurement (ev: four timing
 // events recorded around the three kernels, scripts/clearance_bench.py; else null)
 void launch_clear(hipStream_t s, const ClearArgs& A, hipEvent_t* ev = nullptr);

@@ -534,6 +534,7 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, const double*
   const int npr = (int)N - 1 + M;
   double *cols = nullptr, *copy = nullptr, *dSo = nullptr, *dRo = nullptr, *dresp = nullptr;
   double *clow = nullptr, *clpack = nullptr;   // clearance: the columns' weights; the pack buffer once it exists
+  double *ppath = nullptr, *pgiven = nullptr;  // prediction: the path buffers once they exist
   int* dcls = nullptr;
   SlotBufs sb{};
   int rc = LQRO_OK;
@@ -541,6 +542,8 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, const double*
   if (!rc && M > 0 && own && c->mem.get(copy, (size_t)M * X)) rc = LQRO_E_NOMEM;
   if (!rc && M > 0 && c->mem.get(clow, 2 * (size_t)M)) rc = LQRO_E_NOMEM;
   if (!rc && c->d_clpack && M != c->nobs && c->mem.get(clpack, 5 * (N + M))) rc = LQRO_E_NOMEM;
+  if (!rc && c->d_ppath && M != c->nobs && c->mem.get(ppath, 3 * H * (N + M))) rc = LQRO_E_NOMEM;
+  if (!rc && c->d_pgiven && M != c->nobs && c->mem.get(pgiven, 3 * H * (N + M))) rc = LQRO_E_NOMEM;
   if (!rc && K > 0 && (c->mem.get(dSo, (size_t)K * (3 * NP + 4)) || c->mem.get(dRo, (size_t)K * N * H) ||
                        c->mem.get(dcls, (size_t)M)))
     rc = LQRO_E_NOMEM;
@@ -565,6 +568,7 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, const double*
   if (rc) {
     c->mem.release(cols); c->mem.release(copy); c->mem.release(dSo); c->mem.release(dRo);
     c->mem.release(dresp); c->mem.release(dcls); c->mem.release(clow); c->mem.release(clpack);
+    c->mem.release(ppath); c->mem.release(pgiven);
     slots_release(c, sb);
     (void)pair_set_lds(c->lds_bytes);
     return rc;
@@ -585,6 +589,8 @@ static int set_obstacles(lqro_ctx* c, const double* states, int M, const double*
   c->mem.release(c->d_clow);
   c->d_clow = clow;
   if (clpack) { c->mem.release(c->d_clpack); c->d_clpack = clpack; }
+  if (ppath) { c->mem.release(c->d_ppath); c->d_ppath = ppath; c->pr_kind = 0; }   // (the old paths are gone)
+  if (pgiven) { c->mem.release(c->d_pgiven); c->d_pgiven = pgiven; }
   c->d_cols = cols; c->d_obsown = copy; c->d_So = dSo; c->d_Ro = dRo; c->d_oresp = dresp; c->d_ocls = dcls;
   c->d_obs = M > 0 ? (own ? copy : states) : nullptr;
   c->nobs = M;
@@ -661,6 +667,7 @@ int lqro_set_gains(lqro_ctx* c, const double* A, const double* B, const double* 
   if (err) return LQRO_E_SINGULAR;
   c->per_agent = per_agent ? 1 : 0;
   c->have_gains = 1;
+  c->pcg_stale = 1;   // (the next predicting call rebuilds C G_k)
   return LQRO_OK;
 }
 
@@ -1323,6 +1330,195 @@ int lqro_get_monitor_pairs(lqro_ctx* c, int64_t* pairs, int64_t cap, int64_t* n_
       pairs[2 * n + 1] = h[r].hit[q];
     }
   *n_out = n;
+  return LQRO_OK;
+}
+
+// ---- horizon conflict prediction ------------------------------------------
+static const lqro_predict_total kPredNone = {__builtin_huge_val(), __builtin_huge_val(), -1, -1, -1, -1, -1, -1,
+                                             -1, -1, -1, 0, 0, 0, 0};
+
+// the measurement's buffers, once; the caller has waited for the last step
+static int pred_reserve(lqro_ctx* c) {
+  if (c->d_prtot) return LQRO_OK;
+  const size_t N = c->cfg.n_agents, H = c->cfg.horizon;
+  double *path = nullptr, *pv = nullptr;
+  lqro_predict_row* rows = nullptr;
+  lqro_predict_total* tot = nullptr;
+  int rc = LQRO_OK;
+  if (c->mem.get(path, 3 * H * (N + c->nobs)) || c->mem.get(pv, 3 * N) || c->mem.get(rows, (size_t)c->nrows) ||
+      c->mem.get(tot, 2))
+    rc = LQRO_E_NOMEM;
+  const lqro_predict_total t[2] = {kPredNone, kPredNone};
+  if (!rc && hipMemcpy(tot, t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  if (rc) {
+    c->mem.release(path); c->mem.release(pv); c->mem.release(rows); c->mem.release(tot);
+    return rc;
+  }
+  c->d_ppath = path; c->d_pv = pv; c->d_prrows = rows; c->d_prtot = tot;
+  return LQRO_OK;
+}
+
+// the C G_k buffer for the gains as they are set; the caller has waited for the last step
+static int pred_reserve_cg(lqro_ctx* c) {
+  const int sets = c->per_agent ? c->cfg.n_agents : 1;
+  if (c->d_pcg && c->pcg_sets == sets) return LQRO_OK;
+  double* cg = nullptr;
+  if (c->mem.get(cg, (size_t)sets * c->cfg.horizon * 9)) return LQRO_E_NOMEM;
+  c->mem.release(c->d_pcg);
+  c->d_pcg = cg; c->pcg_sets = sets; c->pcg_stale = 1;
+  return LQRO_OK;
+}
+
+// One prediction on s: from (d_x, d_v), or over the given paths (d_given),
+// the own rows against every column, into `rows`; the totals folded.  The
+// caller has ordered s behind the last step; the buffers exist.
+static int enqueue_predict(lqro_ctx* c, const double* d_x, const double* d_v, const double* d_given,
+                           lqro_predict_row* rows, hipStream_t s, hipEvent_t* ev = nullptr) {
+  const lqro_config& g = c->cfg;
+  if (c->measured) HIPCHK(hipStreamWaitEvent(s, c->cev, 0));   // (the last measurement may be on another stream)
+  PredArgs P{};
+  P.n_agents = g.n_agents; P.nobs = c->nobs; P.X = g.x_dim; P.U = g.u_dim; P.H = g.horizon;
+  P.nrows = c->nrows; P.row_begin = c->rb; P.row_stride = c->rs;
+  P.nsets = c->per_agent ? g.n_agents : 1;
+  P.nc = g.n_agents + c->nobs;
+  P.ncols = d_given ? P.nc : g.n_agents;
+  P.A = c->d_A; P.B = c->d_B; P.L = c->d_L; P.E = c->d_E; P.NCF = c->d_NCF; P.cg = c->d_pcg;
+  P.x = d_x; P.v = d_v; P.obs = c->d_obs; P.ow = c->d_clow;
+  const double a = g.xy_radius + g.xy_radius, b = g.z_radius + g.z_radius;   // as enqueue_clear
+  P.wxy = 1.0 / (a * a); P.wz = 1.0 / (b * b);
+  P.given = d_given; P.path = c->d_ppath;
+  P.rows = rows; P.tot = c->d_prtot;
+  P.active = c->d_actsrc;   // (the caller's bytes, as k_clear reads them)
+  if (!d_given && c->pcg_stale) {
+    LAUNCH(launch_predict_cg(s, P));
+    c->pcg_stale = 0;
+  }
+  LAUNCH(launch_predict(s, P, ev));
+  HIPCHK(hipEventRecord(c->cev, s));
+  c->measured = 1;
+  c->pr_last = rows;
+  c->pr_kind = d_given ? 2 : 1;
+  return LQRO_OK;
+}
+
+static int predict_device(lqro_ctx* c, const double* d_x, const double* d_v, const double* d_given,
+                          lqro_predict_row* d_rows, void* stream) {
+  if (c->pending) return LQRO_E_STATE;
+  if (!d_given && !c->have_gains) return LQRO_E_STATE;
+  HIPCHK(hipSetDevice(c->cfg.device));
+  const int sets = c->per_agent ? c->cfg.n_agents : 1;
+  if (!c->d_prtot || (!d_given && (!c->d_pcg || c->pcg_sets != sets))) {
+    // the first call that needs the buffers: after the last step; later calls never wait
+    HIPCHK(wait_last_step(c));
+    if (int rc = pred_reserve(c)) return rc;
+    if (!d_given)
+      if (int rc = pred_reserve_cg(c)) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (c->stepped) HIPCHK(hipStreamWaitEvent(s, c->ev[3], 0));   // behind the context's last step
+  return enqueue_predict(c, d_x, d_v, d_given, d_rows ? d_rows : c->d_prrows, s);
+}
+
+int lqro_predict_device(lqro_ctx* c, const double* d_x, const double* d_v, lqro_predict_row* d_rows, void* stream) {
+  if (!c || !d_x || !d_v || !clear_radii_ok(c)) return LQRO_E_ARG;
+  return predict_device(c, d_x, d_v, nullptr, d_rows, stream);
+}
+
+int lqro_predict_paths_device(lqro_ctx* c, const double* d_paths, lqro_predict_row* d_rows, void* stream) {
+  if (!c || !d_paths || !clear_radii_ok(c)) return LQRO_E_ARG;
+  return predict_device(c, nullptr, nullptr, d_paths, d_rows, stream);
+}
+
+// the host calls' tail: the rows and this measurement's total out, then the wait
+static int predict_finish(lqro_ctx* c, lqro_predict_row* rows, lqro_predict_total* total) {
+  if (rows)
+    HIPCHK(hipMemcpyAsync(rows, c->d_prrows, sizeof(lqro_predict_row) * (size_t)c->nrows, hipMemcpyDeviceToHost,
+                          c->stream));
+  if (total) HIPCHK(hipMemcpyAsync(total, c->d_prtot, sizeof *total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return LQRO_OK;
+}
+
+int lqro_predict(lqro_ctx* c, const double* x, const double* v, lqro_predict_row* rows, lqro_predict_total* total) {
+  if (!c || !x || !v || !clear_radii_ok(c)) return LQRO_E_ARG;
+  if (c->pending || !c->have_gains) return LQRO_E_STATE;
+  if (int rc = ctx_enter(c, true)) return rc;
+  if (int rc = pred_reserve(c)) return rc;
+  if (int rc = pred_reserve_cg(c)) return rc;
+  const lqro_config& g = c->cfg;
+  HIPCHK(hipMemcpyAsync(c->d_x, x, sizeof(double) * (size_t)g.n_agents * g.x_dim, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_pv, v, sizeof(double) * (size_t)g.n_agents * 3, hipMemcpyHostToDevice, c->stream));
+  if (int rc = enqueue_predict(c, c->d_x, c->d_pv, nullptr, c->d_prrows, c->stream)) return rc;
+  return predict_finish(c, rows, total);
+}
+
+int lqro_predict_paths(lqro_ctx* c, const double* paths, lqro_predict_row* rows, lqro_predict_total* total) {
+  if (!c || !paths || !clear_radii_ok(c)) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  if (int rc = pred_reserve(c)) return rc;
+  const lqro_config& g = c->cfg;
+  const size_t n = 3 * (size_t)g.horizon * ((size_t)g.n_agents + c->nobs);
+  if (!c->d_pgiven && c->mem.get(c->d_pgiven, n)) return LQRO_E_NOMEM;
+  HIPCHK(hipMemcpyAsync(c->d_pgiven, paths, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  if (int rc = enqueue_predict(c, nullptr, nullptr, c->d_pgiven, c->d_prrows, c->stream)) return rc;
+  return predict_finish(c, rows, total);
+}
+
+// scripts/predict_bench.py: one prediction of the device arrays on the
+// context's stream, a measurement like any other, with the launches' own
+// times from HIP events (ms: paths, k_conf, k_conf_obs, k_conf_total).
+// Synchronous; declared where it is used, like the lqro_debug_* hooks.
+int lqro_debug_predict_times(lqro_ctx* c, const double* d_x, const double* d_v, float* ms4) {
+  if (!c || !d_x || !d_v || !ms4 || !clear_radii_ok(c)) return LQRO_E_ARG;
+  if (c->pending || !c->have_gains) return LQRO_E_STATE;
+  if (int rc = ctx_enter(c, true)) return rc;
+  if (int rc = pred_reserve(c)) return rc;
+  if (int rc = pred_reserve_cg(c)) return rc;
+  hipEvent_t ev[5] = {};
+  int rc = LQRO_OK;
+  for (int k = 0; k < 5 && rc == LQRO_OK; ++k)
+    if (hipEventCreate(&ev[k]) != hipSuccess) rc = LQRO_E_HIP;
+  if (rc == LQRO_OK) rc = enqueue_predict(c, d_x, d_v, nullptr, c->d_prrows, c->stream, ev);
+  if (rc == LQRO_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = LQRO_E_HIP;
+  for (int k = 0; k < 4 && rc == LQRO_OK; ++k)
+    if (hipEventElapsedTime(&ms4[k], ev[k], ev[k + 1]) != hipSuccess) rc = LQRO_E_HIP;
+  for (int k = 0; k < 5; ++k)
+    if (ev[k]) (void)hipEventDestroy(ev[k]);
+  return rc;
+}
+
+int lqro_get_prediction(lqro_ctx* c, lqro_predict_total* last, lqro_predict_total* since_reset, int32_t reset) {
+  if (!c) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  lqro_predict_total t[2] = {kPredNone, kPredNone};
+  if (c->d_prtot) HIPCHK(hipMemcpy(t, c->d_prtot, sizeof t, hipMemcpyDeviceToHost));
+  if (last) *last = t[0];
+  if (since_reset) *since_reset = t[1];
+  if (reset && c->d_prtot) HIPCHK(hipMemcpy(c->d_prtot + 1, &kPredNone, sizeof kPredNone, hipMemcpyHostToDevice));
+  return LQRO_OK;
+}
+
+int lqro_get_prediction_rows(lqro_ctx* c, lqro_predict_row* rows, int64_t cap, int64_t* n_out) {
+  if (!c || !n_out || (cap > 0 && !rows)) return LQRO_E_ARG;
+  if (int rc = ctx_enter(c, true)) return rc;
+  *n_out = 0;
+  if (!c->pr_last) return LQRO_OK;
+  if (cap < c->nrows) return LQRO_E_ARG;
+  HIPCHK(hipMemcpy(rows, c->pr_last, sizeof(lqro_predict_row) * (size_t)c->nrows, hipMemcpyDeviceToHost));
+  *n_out = c->nrows;
+  return LQRO_OK;
+}
+
+int lqro_get_paths(lqro_ctx* c, double* out) {
+  if (!c || !out) return LQRO_E_ARG;
+  if (c->pending || c->pr_kind != 1) return LQRO_E_STATE;
+  if (int rc = ctx_enter(c, true)) return rc;
+  const size_t N = c->cfg.n_agents, H = c->cfg.horizon, nc = N + c->nobs;
+  std::vector<double> h(3 * H * nc);   // [k][3][nc] -> [agent][k][3]
+  HIPCHK(hipMemcpy(h.data(), c->d_ppath, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+  for (size_t a = 0; a < N; ++a)
+    for (size_t k = 0; k < H; ++k)
+      for (size_t r = 0; r < 3; ++r) out[(a * H + k) * 3 + r] = h[(k * 3 + r) * nc + a];
   return LQRO_OK;
 }
 

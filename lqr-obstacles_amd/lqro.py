@@ -120,6 +120,59 @@ def merge_clearance(totals) -> dict:
     return out
 
 
+class PredictRow(C.Structure):
+    """lqro_predict_row: one own row's predicted separation over the horizon."""
+    _fields_ = [("s2_min", C.c_double), ("d2_min", C.c_double),
+                ("j_s2", C.c_int32), ("k_s2", C.c_int32), ("j_d2", C.c_int32), ("k_d2", C.c_int32),
+                ("k_first", C.c_int32), ("j_first", C.c_int32), ("n_conf", C.c_int32), ("reserved", C.c_int32),
+                ("conf", C.c_int32 * 4)]
+
+
+class PredictTotal(C.Structure):
+    """lqro_predict_total: the minima, the first hit and the counts over a context's own rows."""
+    _fields_ = [("s2_min", C.c_double), ("d2_min", C.c_double),
+                ("s2_i", C.c_int32), ("s2_j", C.c_int32), ("s2_k", C.c_int32),
+                ("d2_i", C.c_int32), ("d2_j", C.c_int32), ("d2_k", C.c_int32),
+                ("first_k", C.c_int32), ("first_i", C.c_int32), ("first_j", C.c_int32), ("reserved", C.c_int32),
+                ("n_conf", C.c_int64), ("n_rows_conf", C.c_int64), ("n_measured", C.c_int64)]
+
+
+PREDICT_ROW_DTYPE = np.dtype([("s2_min", "<f8"), ("d2_min", "<f8"), ("j_s2", "<i4"), ("k_s2", "<i4"), ("j_d2", "<i4"),
+                              ("k_d2", "<i4"), ("k_first", "<i4"), ("j_first", "<i4"), ("n_conf", "<i4"),
+                              ("reserved", "<i4"), ("conf", "<i4", (4,))])
+assert PREDICT_ROW_DTYPE.itemsize == C.sizeof(PredictRow) == 64 and C.sizeof(PredictTotal) == 80
+PREDICT_TOTAL_FIELDS = tuple(n for n, _ in PredictTotal._fields_)
+PREDICT_TILE = 8   # LQRO_PREDICT_TILE: own rows a workgroup of k_conf
+
+
+def _predict_total_dict(t: PredictTotal) -> dict:
+    return {n: getattr(t, n) for n in PREDICT_TOTAL_FIELDS}
+
+
+def merge_prediction(totals) -> dict:
+    """The ranks' totals of one prediction (or of the same predictions since a
+    reset) as one: each minimum is the smallest (value, i, j, k) over the
+    shards (a +inf minimum has indices -1), the first hit the smallest
+    (k, i, j), the counts are summed, n_measured is the shards' common count
+    (its largest).  Row shards partition the rows, so the merge of a block or
+    cyclic split equals the single context's total of one prediction."""
+    totals = list(totals)
+    out = dict(s2_min=np.inf, d2_min=np.inf, s2_i=-1, s2_j=-1, s2_k=-1, d2_i=-1, d2_j=-1, d2_k=-1, first_k=-1,
+               first_i=-1, first_j=-1, reserved=0, n_conf=0, n_rows_conf=0, n_measured=0)
+    for v in ("s2", "d2"):
+        keys = [(float(t[v + "_min"]), int(t[v + "_i"]), int(t[v + "_j"]), int(t[v + "_k"])) for t in totals
+                if float(t[v + "_min"]) < np.inf]
+        if keys:
+            out[v + "_min"], out[v + "_i"], out[v + "_j"], out[v + "_k"] = min(keys)
+    keys = [(int(t["first_k"]), int(t["first_i"]), int(t["first_j"])) for t in totals if int(t["first_k"]) >= 0]
+    if keys:
+        out["first_k"], out["first_i"], out["first_j"] = min(keys)
+    for k in ("n_conf", "n_rows_conf"):
+        out[k] = sum(int(t[k]) for t in totals)
+    out["n_measured"] = max([int(t["n_measured"]) for t in totals], default=0)
+    return out
+
+
 class LpRow(C.Structure):
     """lqro_lp_row: one own row's result against the plane list its LP saw."""
     _fields_ = [("viol_max", C.c_float), ("hard_viol_max", C.c_float), ("v2", C.c_float), ("dv2", C.c_float),
@@ -209,6 +262,8 @@ EXPORTS = (
     "lqro_get_monitor_rows", "lqro_get_monitor_pairs",
     "lqro_set_lp_audit", "lqro_get_lp_audit", "lqro_get_lp_audit_rows", "lqro_audit_new_v",
     "lqro_set_active", "lqro_set_active_device",
+    "lqro_predict", "lqro_predict_device", "lqro_predict_paths", "lqro_predict_paths_device",
+    "lqro_get_prediction", "lqro_get_prediction_rows", "lqro_get_paths",
 )
 # lqro_set_hard_planes' levels: the planes linearProgram4 does not relax
 LQRO_HARD_NONE, LQRO_HARD_FENCE, LQRO_HARD_HEAD, LQRO_HARD_OBSTACLES = 0, 1, 2, 3
@@ -289,6 +344,14 @@ def lib() -> C.CDLL:
         if hasattr(L, "lqro_set_active"):   # (older libraries in A/B runs lack them)
             L.lqro_set_active.argtypes = [vp, vp]
             L.lqro_set_active_device.argtypes = [vp, vp]
+        if hasattr(L, "lqro_predict"):   # (older libraries in A/B runs lack them)
+            L.lqro_predict.argtypes = [vp, vp, vp, vp, C.POINTER(PredictTotal)]
+            L.lqro_predict_device.argtypes = [vp, vp, vp, vp, vp]
+            L.lqro_predict_paths.argtypes = [vp, vp, vp, C.POINTER(PredictTotal)]
+            L.lqro_predict_paths_device.argtypes = [vp, vp, vp, vp]
+            L.lqro_get_prediction.argtypes = [vp, C.POINTER(PredictTotal), C.POINTER(PredictTotal), i32]
+            L.lqro_get_prediction_rows.argtypes = [vp, vp, i64, C.POINTER(i64)]
+            L.lqro_get_paths.argtypes = [vp, vp]
         L.lqro_set_carry_normal.argtypes = [vp, vp]
         L.lqro_get_carry_normal.argtypes = [vp, vp]
         _lib = L
@@ -624,6 +687,66 @@ class Context:
         n = C.c_int64()
         _check(lib().lqro_get_monitor_pairs(self._h, _p(out), len(out), C.byref(n)), "lqro_get_monitor_pairs")
         return out[:n.value]
+
+    def predict(self, x, v):
+        """Horizon conflict prediction (lqro_predict): with the states x
+        (N, X) and the commanded velocities v (N, 3), each own row's smallest
+        predicted separation over the horizon, its first predicted hit and its
+        conflict columns.  Returns (rows, total): PREDICT_ROW_DTYPE records in
+        row order and this prediction's total; prediction() reads the
+        accumulated ones, paths() the agents' predicted paths."""
+        x = np.ascontiguousarray(x, np.float64)
+        v = np.ascontiguousarray(v, np.float64)
+        if x.shape != (self.cfg.n_agents, self.cfg.x_dim) or v.shape != (self.cfg.n_agents, 3):
+            raise LqroError(f"predict: x {x.shape}, v {v.shape}, expected "
+                            f"{(self.cfg.n_agents, self.cfg.x_dim)} and {(self.cfg.n_agents, 3)}")
+        rows = np.zeros(len(self.row_ids), PREDICT_ROW_DTYPE)
+        t = PredictTotal()
+        _check(lib().lqro_predict(self._h, _p(x), _p(v), _p(rows), C.byref(t)), "lqro_predict")
+        return rows, _predict_total_dict(t)
+
+    def predict_device(self, x_ptr: int, v_ptr: int, rows_ptr: int = 0, stream: int = 0):
+        """The same on device arrays, asynchronous on `stream`, ordered behind
+        the context's last step and measurement (lqro_predict_device)."""
+        _check(lib().lqro_predict_device(self._h, C.c_void_p(x_ptr or None), C.c_void_p(v_ptr or None),
+                                         C.c_void_p(rows_ptr or None), C.c_void_p(stream or None)),
+               "lqro_predict_device")
+
+    def predict_paths(self, paths):
+        """The same measurement over caller-given paths (N + M, H, 3), the
+        obstacle columns the caller's own (lqro_predict_paths)."""
+        paths = np.ascontiguousarray(paths, np.float64)
+        want = (self.cfg.n_agents + self.n_obstacles, self.cfg.horizon, 3)
+        if paths.shape != want:
+            raise LqroError(f"predict_paths: paths has shape {paths.shape}, expected {want}")
+        rows = np.zeros(len(self.row_ids), PREDICT_ROW_DTYPE)
+        t = PredictTotal()
+        _check(lib().lqro_predict_paths(self._h, _p(paths), _p(rows), C.byref(t)), "lqro_predict_paths")
+        return rows, _predict_total_dict(t)
+
+    def predict_paths_device(self, paths_ptr: int, rows_ptr: int = 0, stream: int = 0):
+        _check(lib().lqro_predict_paths_device(self._h, C.c_void_p(paths_ptr or None), C.c_void_p(rows_ptr or None),
+                                               C.c_void_p(stream or None)), "lqro_predict_paths_device")
+
+    def prediction(self, reset: bool = False):
+        """(last, since_reset) prediction totals as dicts (lqro_get_prediction);
+        reset clears the since-reset total after reading it."""
+        a, b = PredictTotal(), PredictTotal()
+        _check(lib().lqro_get_prediction(self._h, C.byref(a), C.byref(b), int(bool(reset))), "lqro_get_prediction")
+        return _predict_total_dict(a), _predict_total_dict(b)
+
+    def prediction_rows(self) -> np.ndarray:
+        """The last prediction's row records (empty before the first)."""
+        rows = np.zeros(len(self.row_ids), PREDICT_ROW_DTYPE)
+        n = C.c_int64()
+        _check(lib().lqro_get_prediction_rows(self._h, _p(rows), len(rows), C.byref(n)), "lqro_get_prediction_rows")
+        return rows[:n.value]
+
+    def paths(self) -> np.ndarray:
+        """The agents' paths (N, H, 3) of the last predict / predict_device."""
+        out = np.zeros((self.cfg.n_agents, self.cfg.horizon, 3))
+        _check(lib().lqro_get_paths(self._h, _p(out)), "lqro_get_paths")
+        return out
 
     def set_lp_audit(self, on, tol: float = 0.0):
         """on: every step audits its own rows at its end, on the step's
@@ -1075,6 +1198,11 @@ class Simulator:
         """Context.clearance on the agents' current estimates q.x."""
         return self.ctx.clearance(np.stack([q.x for q in self.qlist]))
 
+    def predict(self):
+        """Context.predict on the agents' current estimates q.x and the
+        velocities newV the last step() chose."""
+        return self.ctx.predict(np.stack([q.x for q in self.qlist]), np.stack([q.newV for q in self.qlist]))
+
     def set_lp_audit(self, on, tol: float = 0.0):
         """Every step() audits its LP's result on the device (Context.set_lp_audit)."""
         self.ctx.set_lp_audit(on, tol)
@@ -1243,7 +1371,7 @@ class DeviceLoop:
                  p_goal=None, rank: int = 0, world: int = 1, dist=None, device=None,
                  model: Model | None = None, seed: int = 1, stream=None, rows: str = "block",
                  flags: int = LQRO_FLAG_QHULL_ORDER, fence=None, user_planes=None, obstacles=None,
-                 monitor: bool = False, lp_audit=False):
+                 monitor: bool = False, lp_audit=False, predict: bool = False):
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -1279,6 +1407,8 @@ class DeviceLoop:
         # True, or the tolerance itself
         if lp_audit is not False and lp_audit is not None:
             self.ctx.set_lp_audit(1, 0.0 if lp_audit is True else float(lp_audit))
+        # predict: every step() ends with a horizon conflict prediction of (x, newV) (prediction() reads it)
+        self.predict_each = bool(predict)
         self.x = torch.from_numpy(np.ascontiguousarray(x0, np.float64)).to(self.dev)
         self.vgoal = torch.from_numpy(np.ascontiguousarray(vgoal0, np.float64)).to(self.dev)
         self.newv = torch.zeros((n, 3), **f64)
@@ -1331,6 +1461,21 @@ class DeviceLoop:
         merge_lp_audit joins the ranks'."""
         return self.ctx.lp_audit(reset)
 
+    def predict(self):
+        """The horizon conflict prediction of this rank's rows with the
+        velocities the last step() chose, on the loop's stream: an all-gather
+        of newV first when there is more than one rank (a row shard does not
+        hold the other rows' newV), then Context.predict_device(x, newV)."""
+        if self.world > 1:
+            with self.torch.cuda.stream(self.stream):
+                allgather_rows(self.dist, self.newv, self.rank, self.world, mode=self.mode)
+        self.ctx.predict_device(self.x.data_ptr(), self.newv.data_ptr(), 0, self._sid())
+
+    def prediction(self, reset: bool = False):
+        """This rank's (last, since_reset) prediction totals
+        (Context.prediction); merge_prediction joins the ranks'."""
+        return self.ctx.prediction(reset)
+
     def step(self, gather: bool = False):
         """The pair loop for the own rows; newV of the own rows on the device
         (all rows with gather=True: one all-gather of newV)."""
@@ -1347,6 +1492,11 @@ class DeviceLoop:
         if gather and self.world > 1:
             with self.torch.cuda.stream(self.stream):
                 allgather_rows(self.dist, self.newv, self.rank, self.world, mode=self.mode)
+        if self.predict_each:
+            if gather and self.world > 1:   # (newV is whole already)
+                self.ctx.predict_device(self.x.data_ptr(), self.newv.data_ptr(), 0, self._sid())
+            else:
+                self.predict()
         return self.newv
 
     def own_rows(self, t):
