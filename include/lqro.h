@@ -450,6 +450,65 @@ int lqro_set_hard_planes(lqro_ctx* ctx, int32_t level);
 int lqro_set_active(lqro_ctx* ctx, const uint8_t* active /* N, host, copied */);
 int lqro_set_active_device(lqro_ctx* ctx, const uint8_t* d_active /* N, read when the step runs */);
 
+/* ---- interaction classes: who avoids whom, and by how much -----------------
+ * Every agent belongs to one of n_classes classes (cls[i], N bytes indexed by
+ * the global agent id; every row shard takes the same arrays), and
+ * share[a * C + b], in [0, 1], is the factor a row of class a applies against
+ * an AGENT column of class b in place of the reference's fixed 0.5
+ * (LQRO:1416): one fp64 multiply of the pair's distance, rounded once,
+ * wherever the step forms a half-plane.  The reference has no counterpart;
+ * RVO-style libraries ship it as avoidance layers, masks and priorities.
+ * 0.5 in every entry gives the step without a table, bit for bit;
+ * share[a][b] + share[b][a] >= 1 (the two halves cover the whole avoidance) is
+ * the caller's business and is not checked.
+ *   - An ignored pair.  A share of exactly 0.0: row i ignores column j.  The
+ *     slot is treated exactly as lqro_set_active treats an inactive column: no
+ *     pair work, no hull job, its flag written as 0 this step, its record zero
+ *     with i and j set; it adds nothing to the counters, is never named by
+ *     lqro_get_hull_failures or lqro_get_qhmerge_pairs and never listed, marked
+ *     or queued by the schedule.  Any share > 0.0 is live, however small.
+ *   - A pair (i, j < n_agents) is live when row i is active, column j is
+ *     active (lqro_set_active; the two compose) and share[cls[i]][cls[j]] > 0.
+ *     Obstacle columns (j >= n_agents) do not see the table: they keep their
+ *     own responsibility and are never ignored.
+ *   - A row whose every agent column is ignored is still a row: it gets its
+ *     fence, user and obstacle planes and its LP runs (without a plane the LP
+ *     returns vgoal clipped to vmax_lp), unlike an inactive row (newv +0.0).
+ *   - The carried normal runs through the live pairs in (i, j) order, and the
+ *     n_agents x 4 row-normal table follows; a step without a live pair leaves
+ *     the carry as it entered.
+ *   - lqro_get_stats()[0] counts the live slots: for each active own row i the
+ *     active agents of every class b with share[cls[i]][b] > 0, less 1 when
+ *     share[cls[i]][cls[i]] > 0 (itself), plus the obstacle columns (with
+ *     lqro_set_neighbors the kept neighbours, as before).
+ *   - lqro_set_neighbors: a column row i ignores is no candidate of row i and
+ *     uses up none of its K slots; K does not change.
+ *   - Slot numbers and the record count do not move.  Clearance and prediction
+ *     (monitor and explicit calls) do not see the table: they measure bodies,
+ *     not intentions.  The LP audit follows the slots' flags as ever; the
+ *     hard-plane levels are unchanged.  lqro_calculate_new_v*, lqro_audit_new_v
+ *     and lqro_dynamics_step* take no context and do not see it.
+ * cls == NULL or share == NULL clears: the context is then the one that never
+ * had a table, in every launch, size and result.  The share table is copied by
+ * both forms.  The host form checks and copies the class bytes; the device
+ * form keeps the pointer: the bytes are read on the step's stream when the step
+ * runs, so the caller keeps them alive and may rewrite them there before every
+ * step (lqro_set_active_device's contract); a device byte >= n_classes is read
+ * as n_classes - 1.  LQRO_E_ARG: a null context, n_classes outside
+ * 1..LQRO_CLASSES_MAX, a share outside [0, 1] or not finite, a host class byte
+ * >= n_classes.  Both wait for the last enqueued step, return LQRO_E_STATE
+ * while a lqro_step_device_begin is pending, allocate nothing inside a step,
+ * and leave the context as it was when they fail.  The table stays when the
+ * mask, obstacles, fence, user planes, neighbours, hard planes, monitor or
+ * audit are set or cleared, and setting it keeps all of those and the
+ * since-reset totals.  lqro_version() does not change: callers detect the
+ * feature by the symbol. */
+#define LQRO_CLASSES_MAX 16
+int lqro_set_interaction(lqro_ctx* ctx, const uint8_t* cls /* N, host, copied */,
+                         int32_t n_classes, const double* share /* C*C, host, copied */);
+int lqro_set_interaction_device(lqro_ctx* ctx, const uint8_t* d_cls /* N, read when the step runs */,
+                                int32_t n_classes, const double* share /* C*C, host, copied */);
+
 /* One control step: the pair loop LQRO:1393-1436 for the context's rows.
  * x: n_agents*X agent states (Quadrotor::x), vgoal: n_agents*3,
  * newv: n_agents*3 (only rows [row_begin,row_end) are written).  Host

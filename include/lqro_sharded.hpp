@@ -214,6 +214,18 @@ class ShardedSimulator {
     if (ctx_) check(lqro_set_active(ctx_, active.empty() ? nullptr : active.data()), "lqro_set_active");
   }
 
+  // Simulator::setInteraction for this rank's context: every rank passes the
+  // same global class array and table (lqro_set_interaction); an empty cls
+  // clears.
+  void setInteraction(const std::vector<uint8_t>& cls, int32_t n_classes, const std::vector<double>& share) {
+    if (!cls.empty() && (cls.size() != (size_t)n_ || n_classes < 1 ||
+                         share.size() != (size_t)n_classes * (size_t)n_classes))
+      throw std::runtime_error("setInteraction: one byte per agent, n_classes squared shares");
+    if (!ctx_) return;
+    if (cls.empty()) check(lqro_set_interaction(ctx_, nullptr, 0, nullptr), "lqro_set_interaction");
+    else check(lqro_set_interaction(ctx_, cls.data(), n_classes, share.data()), "lqro_set_interaction");
+  }
+
   // One iteration of LQRO:1393-1446 for this rank's rows, then the state
   // exchange; returns the next seed of the rand() stream.  Enqueued only:
   // download() waits for it.

@@ -194,6 +194,23 @@ class Simulator {
     check(lqro_set_active(ctx_, active.empty() ? nullptr : active.data()), "lqro_set_active");
   }
 
+  // Interaction classes (lqro_set_interaction): agent i belongs to class
+  // cls[i] < n_classes, and share[a * n_classes + b] in [0, 1] is the factor a
+  // row of class a applies against an agent column of class b in place of the
+  // reference's 0.5; exactly 0: the row ignores the column.  One byte per
+  // agent and n_classes squared shares; an empty cls clears (no table);
+  // another size throws.
+  void setInteraction(const std::vector<uint8_t>& cls, int32_t n_classes, const std::vector<double>& share) {
+    if (cls.empty()) {
+      check(lqro_set_interaction(ctx_, nullptr, 0, nullptr), "lqro_set_interaction");
+      return;
+    }
+    if (cls.size() != q_.size()) throw std::runtime_error("setInteraction: one byte per agent");
+    if (n_classes < 1 || share.size() != (size_t)n_classes * (size_t)n_classes)
+      throw std::runtime_error("setInteraction: n_classes squared shares");
+    check(lqro_set_interaction(ctx_, cls.data(), n_classes, share.data()), "lqro_set_interaction");
+  }
+
   // Clearance (lqro_clearance): how clear every agent's current estimate
   // Quadrotor::x is of every other agent and obstacle, and of the fence;
   // rows, when given, receives one record per agent.  Returns the total.

@@ -146,7 +146,11 @@ struct __attribute__((visibility("hidden"))) lqro_ctx {
   const unsigned char* d_actsrc;  // n_agents bytes: the caller's, or d_actown (null: no mask)
   unsigned char* d_actown;        // lqro_set_active's copy
   unsigned char* d_act;           // k_active's 0 / 1 bytes, padded to a multiple of 4: what the step's kernels read
-  int act_step;                   // the last step ran under a mask (its pairs counter is k_active's)
+  int act_step;                   // the last step ran under a mask or a table (its pairs counter is k_active's)
+  // interaction classes (lqro_set_interaction[_device]): allocated by the setter, never in a step
+  const unsigned char* d_ixsrc;   // n_agents class bytes: the caller's, or d_ixown (null: no table)
+  unsigned char* d_ixown;         // lqro_set_interaction's copy
+  unsigned char* d_ix;            // an lqro::IxDev: the table, then k_active's clamped bytes: what the step's kernels read
   lqro::PairArgs pa;
   lqro::DevPool mem;              // owns every d_* buffer above that is not the caller's
 };

@@ -131,6 +131,34 @@ __device__ __forceinline__ bool agent_on_u(const unsigned char* act, int agent) 
   return ((w >> (8 * (a & 3))) & 0xFFu) != 0u;
 }
 
+// Interaction classes (lqro_set_interaction) as the step's kernels read them,
+// one device block behind one pointer (null: no table, every agent column
+// takes the 0.5 of LQRO:1416; a kernel's argument block and its scalar
+// registers grow by that pointer alone): the C x C share table the setter
+// copied and k_active's clamped class byte per agent, padded to whole words.
+// share[cls[i] * C + cls[j]] is the factor row i applies against agent column
+// j; exactly 0.0: row i ignores j (the slot is dead, as an inactive column's).
+struct IxDev {
+  double share[256];        // (LQRO_CLASSES_MAX squared)
+  int C;
+  int pad[3];
+  unsigned char cls[4];     // (n_agents + 3) & ~3 bytes
+};
+__device__ __forceinline__ double ix_share(const IxDev* T, int i, int j) {
+  return T->share[(int)T->cls[i] * T->C + (int)T->cls[j]];
+}
+// ... for a pair every lane holds alike (k_pair: a wave takes one pair): the
+// two bytes' words and the entry by scalar loads, as agent_on_u
+__device__ __forceinline__ double ix_share_u(const IxDev* T, int i, int j) {
+  typedef const IxDev __attribute__((address_space(4))) cix;
+  typedef const unsigned int __attribute__((address_space(4))) cword;
+  cix* t = (cix*)(const void*)T;
+  const int a = __builtin_amdgcn_readfirstlane(i), b = __builtin_amdgcn_readfirstlane(j);
+  const unsigned int wa = ((cword*)t->cls)[a >> 2], wb = ((cword*)t->cls)[b >> 2];
+  const int ca = (int)((wa >> (8 * (a & 3))) & 0xFFu), cb = (int)((wb >> (8 * (b & 3))) & 0xFFu);
+  return t->share[ca * t->C + cb];
+}
+
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();

@@ -122,28 +122,37 @@ struct HullArgs {
   const int* ocls;
   const double* oresp;
   int obs_jj;
+  // interaction classes (lqro_set_interaction; null: none): an agent
+  // column's factor is the table's (hull_factor)
+  const IxDev* ix;
 };
 
 // Which of a row's slots are obstacle columns, for the kernels that finish a
 // half-plane outside the hull kernels (k_stale, k_stale_rows): slot jj >= jj
 // (through nbr_list with culling on) takes resp[jj - jj0].  resp null: no
-// obstacles.
+// obstacles.  ix: the interaction table (null: none) an agent slot
+// takes its factor from; nbr_list is set with either.
 struct ObsSlots {
   const double* resp;
   const int* nbr_list;
   int jj;
+  const IxDev* ix;
 };
 
-// the factor of LQRO:1416 for a slot's half-plane: 0.5 between agents, the
+// the factor of LQRO:1416 for a slot's half-plane: 0.5 between agents, or the
+// share of the row's class against the column's (lqro_set_interaction); the
 // obstacle's own responsibility for an obstacle column (LQRO:1434: 1.0)
 __device__ __forceinline__ double slot_factor(const int* nbr_list, int npr, long slot, const double* oresp,
-                                              int obs_jj) {
-  if (!oresp) return 0.5;
+                                              int obs_jj, const IxDev* ix, int row_begin, int row_stride) {
+  if (!oresp && !ix) return 0.5;
   const int jj = nbr_list ? nbr_list[slot] : (int)(slot % npr);
-  return jj >= obs_jj ? oresp[jj - obs_jj] : 0.5;
+  if (oresp && jj >= obs_jj) return oresp[jj - obs_jj];
+  if (!ix) return 0.5;
+  const int i = row_begin + (int)(slot / npr) * row_stride;
+  return ix_share(ix, i, jj < i ? jj : jj + 1);
 }
 __device__ __forceinline__ double hull_factor(const HullArgs& A, int slot) {
-  return slot_factor(A.nbr_list, A.npr, slot, A.oresp, A.obs_jj);
+  return slot_factor(A.nbr_list, A.npr, slot, A.oresp, A.obs_jj, A.ix, A.row_begin, A.row_stride);
 }
 // the point set of the column whose state is xj (x's rows past the agents'
 // are the obstacles'): its class's

@@ -72,7 +72,11 @@ struct PairArgs {
   // whose row or agent column is inactive.  The hot launches evaluate what
   // they are given and do not test the mask; today the producers are k_prio
   // (lists none), k_prio_prev (copies the list k_active has filtered) and
-  // lqro_set_obstacles (empties it)
+  // lqro_set_obstacles (empties it).  The same holds under an interaction table
+  // (`ix` below) for a pair the row ignores: no entry may name a pair that is
+  // not live, which is row active, column active and, for an agent column,
+  // share[cls[i]][cls[j]] > 0.  The same three producers keep it: k_prio
+  // tests the pair predicate, k_active filters the carried-over list by it
   const int* hot_list;
   const unsigned char* hot_mark;      // per slot: 1 = in the hot list
   const int* hot_count;
@@ -115,7 +119,17 @@ struct PairArgs {
   // the carried-over list, k_prio lists none), and with culling the neighbour
   // lists hold none either (k_nbr)
   const unsigned char* active;
+  // interaction classes (lqro_set_interaction; null: none).  do_pair
+  // reads the factor of LQRO:1416 for an agent column from the table in every
+  // instantiation (the hot launches evaluate listed pairs): one wave-uniform
+  // branch on the null pointer, then scalar loads.  The pair predicate (a
+  // share of exactly 0.0: the slot is dead) is tested where the mask is, by
+  // the row launch's MASK instantiation, which a table selects as a mask does
+  const IxDev* ix;
 };
+
+// the row launch runs its MASK instantiation, and the side tails do not sweep
+inline bool pair_masked(const PairArgs& P) { return P.active != nullptr || P.ix != nullptr; }
 
 struct BlockTabs {
   const double* T;
@@ -747,7 +761,15 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
       flags = LQRO_REC_PLANE | (inside ? LQRO_REC_INSIDE : 0) | (go.backup ? LQRO_REC_BACKUP : 0);
       dist = distance;
       if (!inside) {
-        distance *= obs ? P.oresp[jq - P.obs_jj] : 0.5;         // :1416 (an obstacle: LQRO:1434, its own share)
+        // :1416 (an obstacle: LQRO:1434, its own share; between agents the classes' share, lqro_set_interaction)
+        // (the pair's ids rebuilt from lrow and jq, which live this long anyway, in scalar registers)
+        double fac = 0.5;
+        if (P.ix != nullptr && !obs) {
+          const int ri = __builtin_amdgcn_readfirstlane(P.row_begin + lrow * P.row_stride);
+          const int rq = __builtin_amdgcn_readfirstlane(jq);
+          fac = ix_share_u(P.ix, ri, rq < ri ? rq : rq + 1);
+        }
+        distance *= obs ? P.oresp[jq - P.obs_jj] : fac;
         const double mult = -1.0;                               // :1215
         pl[0] = (float)(xi[3] + mult * distance * nrm[0]);      // :1217
         pl[1] = (float)(xi[4] + mult * distance * nrm[1]);
@@ -884,7 +906,8 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
   // costs balance inside the row.  Agent i's horizon tables are staged into
   // LDS only when they change (once per workgroup with shared gains).
   //
-  // A slot whose row or column is inactive (lqro_set_active): no plane, flag
+  // A slot whose row or column is inactive (lqro_set_active), or whose agent
+  // column the row ignores (lqro_set_interaction): no plane, flag
   // 0 written this step, and the zero record with the pair's ids.  Lane 0
   // writes inside one `if` that every lane leaves together: the caller's
   // `continue` must be reached by the whole wave at once.  (A lane that
@@ -908,6 +931,8 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
   // (with culling the neighbour lists carry the mask: an inactive row's list
   // is all -1, no list names an inactive column)
   const unsigned char* act = MASK && P.nbr_list == nullptr ? P.active : nullptr;
+  // (... and the table: k_nbr keeps no column its row ignores)
+  const bool ixon = MASK && P.nbr_list == nullptr && P.ix != nullptr;
   long staged = -1;
   for (;;) {
     // work unit = (row, part): a row is split into row_split pair ranges
@@ -951,8 +976,13 @@ __device__ __forceinline__ void pair_block(const PairArgs& P, double* lds) {
     if (lane == 0) jj = atomicAdd(&s_next, 1);
     jj = __builtin_amdgcn_readlane(jj, 0);
     if (jj >= jj_end) break;
-    if constexpr (MASK) if (act != nullptr) {   // (jj < obs_jj: an agent column, jj-th other agent of row i)
-      if (!row_on || (jj < P.obs_jj && !agent_on_u(act, jj < i ? jj : jj + 1))) {
+    if constexpr (MASK) if (act != nullptr || ixon) {   // (jj < obs_jj: an agent column, jj-th other agent of row i)
+      bool dead = !row_on;   // (wave-uniform: i and jj are)
+      if (!dead && jj < P.obs_jj) {
+        const int j = jj < i ? jj : jj + 1;
+        dead = (act != nullptr && !agent_on_u(act, j)) || (ixon && !(ix_share_u(P.ix, i, j) > 0.0));
+      }
+      if (dead) {
         skip_slot(i, lrow, jj);
         continue;
       }
@@ -1023,7 +1053,7 @@ __global__ void __launch_bounds__(LQRO_PAIR_LB) k_pair(PairArgs P) {
 __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int row_begin, int row_stride, int npr,
                                             double r2,
                                             int k, int K, int* list, unsigned long long* stats,
-                                            const unsigned char* act, int n_agents) {
+                                            const unsigned char* act, int n_agents, const IxDev* ix) {
   constexpr int kCap = 1024;   // candidates within r held in LDS
   __shared__ double cd[kCap];
   __shared__ int cj[kCap];
@@ -1032,7 +1062,14 @@ __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int r
   // candidate, an inactive row has none (its list is all -1); obstacle
   // columns (j >= n_agents) are not masked
   const bool row_on = act == nullptr || act[i] != 0;
-  auto on = [&](int j) { return act == nullptr || (row_on && (j >= n_agents || act[j] != 0)); };
+  // interaction classes (lqro_set_interaction; ix null: none): an agent
+  // the row ignores is no candidate either, so it uses up none of the K slots
+  auto on = [&](int j) {
+    if (!row_on) return false;
+    if (j >= n_agents) return true;
+    if (act != nullptr && act[j] == 0) return false;
+    return ix == nullptr || ix_share(ix, i, j) > 0.0;
+  };
   const double* xi = x + (size_t)i * X;
   // one scan: the agents within r (ascending j), usually a few dozen
   int ncand = 0;
@@ -1121,7 +1158,7 @@ __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int r
 }
 
 // k_active: the activity mask at the head of a step (lqro_set_active; one
-// workgroup, launched only with a mask set).  The caller's bytes (the device
+// workgroup, launched only with a mask or an interaction table set).  The caller's bytes (the device
 // form's may change between steps) become the 0 / 1 bytes the step's kernels
 // read, whole words; the pairs statistic, the slots the sweep visits: for each
 // active own row the active agents other than itself plus the n_obs obstacle
@@ -1132,25 +1169,45 @@ __global__ void __launch_bounds__(64) k_nbr(const double* x, int X, int N, int r
 // the side stream's first hot launch and the speculative hull queue is active.
 // An inactive own row's newV is the LP launch's (lp_row writes +0.0).
 struct ActiveArgs {
-  const unsigned char* src;   // n_agents bytes, the caller's
-  unsigned char* act;         // (n_agents + 3) & ~3 bytes
+  const unsigned char* src;   // n_agents bytes, the caller's (null: no mask, everybody takes part)
+  unsigned char* act;         // (n_agents + 3) & ~3 bytes (null with src)
   int n_agents, n_obs, npr;
   int nrows, row_begin, row_stride;
   unsigned long long* pairs;
   int* prev;
   int* prevn;
   int cap;
+  // interaction classes (lqro_set_interaction; clsrc null: none): the
+  // caller's class bytes become the clamped bytes the step's kernels read (a
+  // byte >= C reads as C - 1), whole words, behind the table in ix
+  const unsigned char* clsrc;   // n_agents bytes, the caller's
+  IxDev* ix;
 };
 
+// With a table (alone or with a mask) the kernel is the head of the step for
+// both: the pairs statistic counts the live slots, for each active own row i
+// the active agents of every class b with share[cls_i][b] > 0, less itself
+// when share[cls_i][cls_i] > 0, plus the obstacle columns; and the carried-over
+// list keeps the live pairs only (row active, column active, share > 0).
 __global__ void __launch_bounds__(256) k_active(ActiveArgs A) {
-  __shared__ int n_on, n_rows_on;
-  if (threadIdx.x == 0) { n_on = 0; n_rows_on = 0; }
+  __shared__ int n_on, n_rows_on, n_cls[LQRO_CLASSES_MAX];
+  __shared__ unsigned long long n_live;
+  if (threadIdx.x == 0) { n_on = 0; n_rows_on = 0; n_live = 0; }
+  if (threadIdx.x < LQRO_CLASSES_MAX) n_cls[threadIdx.x] = 0;
   __syncthreads();
   const int npad = (A.n_agents + 3) & ~3;
+  auto on_src = [&](int q) { return A.src == nullptr || A.src[q] != 0; };
+  const int C = A.clsrc != nullptr ? A.ix->C : 1;
+  auto cls_src = [&](int q) { return min((int)A.clsrc[q], C - 1); };
   int mine = 0, rows = 0;
   for (int q = threadIdx.x; q < npad; q += blockDim.x) {
-    const bool on = q < A.n_agents && A.src[q] != 0;
-    A.act[q] = on ? 1 : 0;
+    const bool on = q < A.n_agents && on_src(q);
+    if (A.act != nullptr) A.act[q] = on ? 1 : 0;
+    if (A.clsrc != nullptr) {
+      const int cl = q < A.n_agents ? cls_src(q) : 0;
+      A.ix->cls[q] = (unsigned char)cl;
+      if (on) atomicAdd(&n_cls[cl], 1);
+    }
     mine += on ? 1 : 0;
     const int d = q - A.row_begin;   // an own row: row_begin + r row_stride, r < nrows
     if (on && d >= 0 && d % A.row_stride == 0 && d / A.row_stride < A.nrows) ++rows;
@@ -1158,8 +1215,24 @@ __global__ void __launch_bounds__(256) k_active(ActiveArgs A) {
   if (mine) atomicAdd(&n_on, mine);
   if (rows) atomicAdd(&n_rows_on, rows);
   __syncthreads();
-  if (threadIdx.x == 0 && A.pairs != nullptr)
+  if (A.clsrc != nullptr && A.pairs != nullptr) {   // (block-uniform)
+    unsigned long long live = 0;
+    for (int r = threadIdx.x; r < A.nrows; r += blockDim.x) {
+      const int i = A.row_begin + r * A.row_stride;
+      if (!on_src(i)) continue;
+      const double* sh = A.ix->share + cls_src(i) * C;
+      int n = A.n_obs;
+      for (int b = 0; b < C; ++b)
+        if (sh[b] > 0.0) n += n_cls[b];
+      if (sh[cls_src(i)] > 0.0) --n;
+      live += (unsigned long long)n;
+    }
+    if (live) atomicAdd(&n_live, live);
+    __syncthreads();
+    if (threadIdx.x == 0) *A.pairs = n_live;
+  } else if (threadIdx.x == 0 && A.pairs != nullptr) {
     *A.pairs = (unsigned long long)n_rows_on * (unsigned long long)(max(n_on - 1, 0) + A.n_obs);
+  }
   if (A.prev == nullptr || threadIdx.x >= 64) return;
   // one wave, 64 entries a pass: a pass is read before it is written, and
   // nothing is written ahead of what was read
@@ -1174,7 +1247,8 @@ __global__ void __launch_bounds__(256) k_active(ActiveArgs A) {
     if (keep) {
       const int lrow = slot / A.npr, jj = slot - lrow * A.npr;
       const int i = A.row_begin + lrow * A.row_stride, j = jj < i ? jj : jj + 1;
-      keep = A.src[i] != 0 && (j >= A.n_agents || A.src[j] != 0);
+      keep = on_src(i) && (j >= A.n_agents ||
+                           (on_src(j) && (A.clsrc == nullptr || A.ix->share[cls_src(i) * C + cls_src(j)] > 0.0)));
     }
     const unsigned long long bal = __ballot(keep);
     if (keep) A.prev[kept + __popcll(bal & ((1ull << lane) - 1ull))] = slot;
@@ -1218,6 +1292,10 @@ struct PrioArgs {
   // or agent column (j < n_agents) is inactive is never listed, marked or queued
   const unsigned char* act;
   int n_agents;
+  // interaction classes (lqro_set_interaction; ix null: none, act may
+  // then be null under k_prio<true>): nor is a pair whose agent column the row
+  // ignores (a share of exactly 0.0)
+  const IxDev* ix;
 };
 
 // the last step's inside-hull pairs at the head of the hot list (one block)
@@ -1311,7 +1389,7 @@ __global__ void __launch_bounds__(256) k_prio_save(const int* hq, const int* hco
   if (threadIdx.x == 0) *prevn = m;
 }
 
-// (MASK: under an activity mask; without it the kernel is the one a context
+// (MASK: under an activity mask or an interaction table; without it the kernel is the one a context
 // without a mask always ran, on the step's critical path ahead of the sweep)
 template <bool MASK>
 __global__ void __launch_bounds__(256) k_prio(PrioArgs A) {
@@ -1333,7 +1411,10 @@ __global__ void __launch_bounds__(256) k_prio(PrioArgs A) {
       t = fmin(fmax(t, 0.0), A.t_hot);
       const double e0 = p0 + t * v0, e1 = p1 + t * v1, e2 = p2 + t * v2;
       hot = e0 * e0 + e1 * e1 + e2 * e2 <= A.r2_hot;
-      if constexpr (MASK) hot = hot && A.act[i] != 0 && (j >= A.n_agents || A.act[j] != 0);
+      if constexpr (MASK) {
+        if (A.act != nullptr) hot = hot && A.act[i] != 0 && (j >= A.n_agents || A.act[j] != 0);
+        if (A.ix != nullptr) hot = hot && (j >= A.n_agents || ix_share(A.ix, i, j) > 0.0);
+      }
     }
     const unsigned long long b = __ballot(hot);
     int pos = 0;

@@ -51,7 +51,7 @@ void launch_qside_t(dim3 grid, hipStream_t s, const HullArgs& H, const PairArgs&
 template <int X, bool R>
 void launch_pair_t(dim3 grid, dim3 block, size_t lds, hipStream_t s, const PairArgs& P) {
   const int h = P.hot_only == 0 ? kRowLaunch : (P.per_agent ? kHotPerAgent : kHotShared);
-  if (h == kRowLaunch && P.active) hipLaunchKernelGGL((k_pair<X, R, kRowLaunch, true>), grid, block, lds, s, P);
+  if (h == kRowLaunch && pair_masked(P)) hipLaunchKernelGGL((k_pair<X, R, kRowLaunch, true>), grid, block, lds, s, P);
   else if (h == kRowLaunch) hipLaunchKernelGGL((k_pair<X, R, kRowLaunch>), grid, block, lds, s, P);
   else if (h == kHotShared) hipLaunchKernelGGL((k_pair<X, R, kHotShared>), grid, block, lds, s, P);
   else hipLaunchKernelGGL((k_pair<X, R, kHotPerAgent>), grid, block, lds, s, P);

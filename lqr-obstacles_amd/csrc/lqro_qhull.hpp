@@ -1477,7 +1477,7 @@ __global__ void __launch_bounds__(64) k_stale(float* planes, const double* qnrm,
     const int lrow = (int)(slot / npr);
     const int i = row_begin + lrow * row_stride;
     const double* xi = x + (size_t)i * X;
-    const double dh = qnrm[(size_t)slot * 4 + 3] * slot_factor(O.nbr_list, npr, slot, O.resp, O.jj);   // :1416
+    const double dh = qnrm[(size_t)slot * 4 + 3] * slot_factor(O.nbr_list, npr, slot, O.resp, O.jj, O.ix, row_begin, row_stride);   // :1416
     const double mult = 1.0;                              // :1213
     float* pl = planes + (size_t)slot * 8;
     pl[0] = (float)(xi[3] + mult * dh * nrm[0]);
@@ -1572,7 +1572,7 @@ __global__ void __launch_bounds__(64) k_stale_rows(float* planes, const double* 
     }
     if (lane != 0) continue;
     const double* xi = x + (size_t)i * X;
-    const double dh = qnrm[(size_t)s0 * 4 + 3] * slot_factor(O.nbr_list, npr, s0, O.resp, O.jj);   // :1416
+    const double dh = qnrm[(size_t)s0 * 4 + 3] * slot_factor(O.nbr_list, npr, s0, O.resp, O.jj, O.ix, row_begin, row_stride);   // :1416
     const double mult = 1.0;                            // :1213
     float* pl = planes + (size_t)s0 * 8;
     pl[0] = (float)(xi[3] + mult * dh * nrm[0]);

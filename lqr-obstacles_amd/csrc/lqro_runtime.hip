@@ -471,6 +471,63 @@ int lqro_set_active(lqro_ctx* c, const uint8_t* active) { return set_active(c, a
 
 int lqro_set_active_device(lqro_ctx* c, const uint8_t* d_active) { return set_active(c, d_active, false); }
 
+// lqro_set_interaction[_device].  own: `cls` is a host array to check and copy.
+static int set_interaction(lqro_ctx* c, const uint8_t* cls, int32_t n_classes, const double* share, bool own) {
+  if (!c) return LQRO_E_ARG;
+  if (c->pending) return LQRO_E_STATE;   // the pending half-step's tail was enqueued under the old table
+  const size_t N = (size_t)c->cfg.n_agents;
+  if (cls && share) {
+    if (n_classes < 1 || n_classes > LQRO_CLASSES_MAX) return LQRO_E_ARG;
+    for (int q = 0; q < n_classes * n_classes; ++q)
+      if (!(share[q] >= 0.0 && share[q] <= 1.0)) return LQRO_E_ARG;   // (a NaN fails both)
+    if (own)
+      for (size_t q = 0; q < N; ++q)
+        if (cls[q] >= n_classes) return LQRO_E_ARG;
+  }
+  if (int rc = ctx_enter(c, false)) return rc;
+  if (!cls || !share) {   // the context that never had a table: no buffer, no launch
+    c->mem.release(c->d_ixown);
+    c->mem.release(c->d_ix);
+    c->d_ixsrc = nullptr;
+    return LQRO_OK;
+  }
+  // every new buffer first: a failed call leaves the context as it was
+  static_assert(sizeof(((IxDev*)nullptr)->share) == sizeof(double) * LQRO_CLASSES_MAX * LQRO_CLASSES_MAX, "IxDev::share");
+  IxDev head{};
+  for (int q = 0; q < n_classes * n_classes; ++q) head.share[q] = share[q];
+  head.C = n_classes;
+  unsigned char *copy = nullptr, *dix = nullptr;
+  int rc = LQRO_OK;
+  if (c->mem.get(dix, offsetof(IxDev, cls) + ((N + 3) & ~(size_t)3), 0)) rc = LQRO_E_NOMEM;
+  if (!rc && own && c->mem.get(copy, N)) rc = LQRO_E_NOMEM;
+  // (the stream the step reads them on may be non-blocking: the copies are synchronous)
+  if (!rc && hipMemcpy(dix, &head, offsetof(IxDev, cls), hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  if (!rc && own && hipMemcpy(copy, cls, N, hipMemcpyHostToDevice) != hipSuccess) rc = LQRO_E_HIP;
+  if (rc) {
+    c->mem.release(dix); c->mem.release(copy);
+    return rc;
+  }
+  c->mem.release(c->d_ix);
+  c->d_ix = dix;
+  c->mem.release(c->d_ixown);
+  c->d_ixown = copy;
+  c->d_ixsrc = own ? copy : cls;
+  return LQRO_OK;
+}
+
+int lqro_set_interaction(lqro_ctx* c, const uint8_t* cls, int32_t n_classes, const double* share) {
+  return set_interaction(c, cls, n_classes, share, true);
+}
+
+int lqro_set_interaction_device(lqro_ctx* c, const uint8_t* d_cls, int32_t n_classes, const double* share) {
+  return set_interaction(c, d_cls, n_classes, share, false);
+}
+
+// the interaction table as the step's kernels read it (null: none)
+static const IxDev* ix_tab(const lqro_ctx* c) {
+  return c->d_ixsrc ? reinterpret_cast<const IxDev*>(c->d_ix) : nullptr;
+}
+
 int lqro_set_hard_planes(lqro_ctx* c, int32_t level) {
   if (!c || level < LQRO_HARD_NONE || level > LQRO_HARD_OBSTACLES) return LQRO_E_ARG;
   if (c->pending) return LQRO_E_STATE;   // the pending half-step's LP was planned with the old level
@@ -741,6 +798,7 @@ static PairArgs pair_args(const lqro_ctx* c, const StepPlan& plan, const double*
   P.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;   // (k_nbr fills it)
   P.rowpend = plan.early ? c->d_rowpend : nullptr;
   P.active = c->d_actsrc ? c->d_act : nullptr;
+  P.ix = ix_tab(c);
   if (plan.hot) {
     P.hot_list = c->d_hotlist; P.hot_mark = c->d_hotmark; P.hot_count = c->d_hcount + LQRO_HC_HOT;
     P.hot_next = c->d_hcount + LQRO_HC_HOT_NEXT; P.hot_cap = c->hot_cap;
@@ -771,7 +829,7 @@ static PrioArgs prio_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
   Q.t_hot = c->knobs.hot_t; Q.r2_hot = c->knobs.hot_r * c->knobs.hot_r;   // seconds, metres (scheduling heuristic)
   Q.list = c->d_hotlist; Q.mark = c->d_hotmark; Q.count = c->d_hcount + LQRO_HC_HOT; Q.cap = c->hot_cap;
   Q.rowpend = P.rowpend;
-  Q.act = P.active; Q.n_agents = c->cfg.n_agents;
+  Q.act = P.active; Q.n_agents = c->cfg.n_agents; Q.ix = P.ix;
   if (plan.split) {
     Q.prev = c->d_prevq; Q.prevn = c->d_hot2 + LQRO_H2_PREV; Q.hot1n = c->d_hot2 + LQRO_H2_HOT1;
     Q.hot2next = c->d_hot2 + LQRO_H2_HOT2_NEXT;
@@ -790,6 +848,7 @@ static HullArgs hull_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
   if (c->nobs > 0) { Hh.So = P.So; Hh.ocls = P.ocls; Hh.oresp = P.oresp; Hh.obs_jj = P.obs_jj; }
   Hh.row_begin = c->rb; Hh.row_stride = c->rs; Hh.npr = plan.npr; Hh.per_agent = c->per_agent;
   Hh.nbr_list = P.nbr_list;
+  Hh.ix = P.ix;
   Hh.r2 = P.r2; Hh.r2_lo = P.r2_lo; Hh.r2_hi = P.r2_hi;
   Hh.T = c->d_T; Hh.NCF = c->d_NCF; Hh.S = c->d_S; Hh.x = P.x;
   Hh.planes = c->d_planes; Hh.recs = c->d_recs;
@@ -826,9 +885,11 @@ static HullArgs hull_args(const lqro_ctx* c, const StepPlan& plan, const PairArg
 static ObsSlots obs_slots(const lqro_ctx* c) {
   ObsSlots O{};
   if (c->nobs > 0) {
-    O.resp = c->d_oresp; O.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;
+    O.resp = c->d_oresp;
     O.jj = c->cfg.n_agents - 1;
   }
+  O.ix = ix_tab(c);
+  if (c->nobs > 0 || O.ix) O.nbr_list = c->nbr_k > 0 ? c->d_nbrlist : nullptr;
   return O;
 }
 
@@ -889,10 +950,12 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
   // Qhull order: the normal the last step's last eligible pair left enters this step
   if (c->qhull_order)
     HIPCHK(hipMemcpyAsync(c->d_carry, c->d_carry + 3, sizeof(double) * 3, hipMemcpyDeviceToDevice, s));
-  // the activity mask: this step's bytes, its pairs counter, the carried-over list without the pairs that left
-  if (c->d_actsrc) {
+  // the activity mask and the interaction table: this step's bytes, its pairs counter, the carried-over list
+  // without the pairs that left or are ignored now
+  if (c->d_actsrc || c->d_ixsrc) {
     ActiveArgs Aa{};
-    Aa.src = c->d_actsrc; Aa.act = c->d_act;
+    if (c->d_actsrc) { Aa.src = c->d_actsrc; Aa.act = c->d_act; }
+    if (c->d_ixsrc) { Aa.clsrc = c->d_ixsrc; Aa.ix = reinterpret_cast<IxDev*>(c->d_ix); }
     Aa.n_agents = g.n_agents; Aa.n_obs = c->nobs; Aa.npr = c->npr;
     Aa.nrows = c->nrows; Aa.row_begin = c->rb; Aa.row_stride = c->rs;
     Aa.pairs = c->nbr_k > 0 ? nullptr : c->d_stats + LQRO_ST_PAIRS;
@@ -901,7 +964,7 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
   }
   if (c->nbr_k > 0) {
     LAUNCH(hipLaunchKernelGGL(k_nbr, dim3((unsigned)c->nrows), dim3(64), 0, s, P.x, g.x_dim, g.n_agents + c->nobs, c->rb, c->rs,
-                              c->npr, c->nbr_r2, c->nbr_k, plan.npr, c->d_nbrlist, c->d_stats, P.active, g.n_agents));
+                              c->npr, c->nbr_r2, c->nbr_k, plan.npr, c->d_nbrlist, c->d_stats, P.active, g.n_agents, P.ix));
   }
   if (plan.early) HIPCHK(hipMemsetAsync(c->d_rowpend, 0, sizeof(int) * 2 * (size_t)c->nrows, s));
   if (c->nfence > 0) {   // this step's fence planes, before any LP can start
@@ -924,7 +987,7 @@ static int enqueue_prologue(lqro_ctx* c, const StepPlan& plan, const PairArgs& P
       LAUNCH(hipLaunchKernelGGL(k_prio_prev, dim3(1), dim3(256), 0, s, Q));
     }
     const long nb = std::min<long>((plan.slots + 255) / 256, 8L * c->n_cu);
-    if (Q.act) LAUNCH(hipLaunchKernelGGL(k_prio<true>, dim3((unsigned)nb), dim3(256), 0, s, Q));
+    if (Q.act || Q.ix) LAUNCH(hipLaunchKernelGGL(k_prio<true>, dim3((unsigned)nb), dim3(256), 0, s, Q));
     else LAUNCH(hipLaunchKernelGGL(k_prio<false>, dim3((unsigned)nb), dim3(256), 0, s, Q));
   }
   return LQRO_OK;
@@ -944,7 +1007,7 @@ static int enqueue_side(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, co
     if (plan.qside) {
       PairArgs Pq = P;
       Pq.max_waves = plan.qside_waves;
-      if (plan.nside == 0 || P.active) Pq.nrows = 0;   // (under a mask the main stream's row launch sweeps every row)
+      if (plan.nside == 0 || pair_masked(P)) Pq.nrows = 0;   // (under a mask or a table the main stream's row launch sweeps every row)
       LAUNCH(launch_qside(x_dim, dim3(std::min(nwait, c->qworkers)), c->side, Hh, Pq));
     } else {
       if (!c->knobs.qhull_big) {
@@ -968,7 +1031,7 @@ static int enqueue_side(lqro_ctx* c, const StepPlan& plan, const PairArgs& P, co
   } else {
     PairArgs Pt = P;
     Pt.max_waves = plan.side_waves;
-    if (plan.nside == 0 || P.active) Pt.nrows = 0;   // (as k_qside's tail)
+    if (plan.nside == 0 || pair_masked(P)) Pt.nrows = 0;   // (as k_qside's tail)
     LAUNCH(launch_side(x_dim, dim3(nwait), dim3(HULL_CTHREADS), c->side, Hh, Pt));
   }
   return LQRO_OK;
@@ -1095,7 +1158,7 @@ static int enqueue_step(lqro_ctx* c, const double* d_x, const double* d_vgoal, d
   double* d_lpnv = d_newv != nullptr ? d_newv : (phase == 1 ? c->d_newv : nullptr);   // the early LP's newV
   const StepPlan plan = plan_step(step_shape(c, phase, d_lpnv, d_newv), c->knobs, fb, fb.inside != ~0ull);
   c->early_step = plan.early ? 1 : 0;
-  c->act_step = c->d_actsrc ? 1 : 0;
+  c->act_step = c->d_actsrc || c->d_ixsrc ? 1 : 0;
   c->early_internal = plan.early_internal ? 1 : 0;
   // 2. the kernels' arguments
   const PairArgs P = pair_args(c, plan, c->nobs > 0 ? c->d_cols : d_x);   // (k_cols fills d_cols in the prologue)

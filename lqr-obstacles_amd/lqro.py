@@ -262,11 +262,13 @@ EXPORTS = (
     "lqro_get_monitor_rows", "lqro_get_monitor_pairs",
     "lqro_set_lp_audit", "lqro_get_lp_audit", "lqro_get_lp_audit_rows", "lqro_audit_new_v",
     "lqro_set_active", "lqro_set_active_device",
+    "lqro_set_interaction", "lqro_set_interaction_device",
     "lqro_predict", "lqro_predict_device", "lqro_predict_paths", "lqro_predict_paths_device",
     "lqro_get_prediction", "lqro_get_prediction_rows", "lqro_get_paths",
 )
 # lqro_set_hard_planes' levels: the planes linearProgram4 does not relax
 LQRO_HARD_NONE, LQRO_HARD_FENCE, LQRO_HARD_HEAD, LQRO_HARD_OBSTACLES = 0, 1, 2, 3
+LQRO_CLASSES_MAX = 16   # lqro_set_interaction's classes
 
 NORMALS_PER_AGENT = 22   # LQRO_NORMALS_PER_AGENT: 16 propagate + 6 observation
 
@@ -344,6 +346,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "lqro_set_active"):   # (older libraries in A/B runs lack them)
             L.lqro_set_active.argtypes = [vp, vp]
             L.lqro_set_active_device.argtypes = [vp, vp]
+        if hasattr(L, "lqro_set_interaction"):   # (as above)
+            L.lqro_set_interaction.argtypes = [vp, vp, i32, vp]
+            L.lqro_set_interaction_device.argtypes = [vp, vp, i32, vp]
         if hasattr(L, "lqro_predict"):   # (older libraries in A/B runs lack them)
             L.lqro_predict.argtypes = [vp, vp, vp, vp, C.POINTER(PredictTotal)]
             L.lqro_predict_device.argtypes = [vp, vp, vp, vp, vp]
@@ -486,6 +491,7 @@ class Context:
         self.n_obstacles = 0
         self._obs_keep = None      # a device tensor given to set_obstacles, kept alive
         self._act_keep = None      # ... and one given to set_active
+        self._ix_keep = None       # ... and one given to set_interaction
 
     def close(self):
         if self._h:
@@ -623,6 +629,55 @@ class Context:
         m = np.ascontiguousarray(m != 0, dtype=np.uint8)
         _check(lib().lqro_set_active(self._h, _p(m)), "lqro_set_active")
         self._act_keep = None
+
+    def set_interaction(self, cls, share, device=False):
+        """Interaction classes (lqro_set_interaction): agent i belongs to class
+        cls[i], and share[a][b] in [0, 1] is the factor a row of class a applies
+        against an agent column of class b in place of the reference's 0.5; a
+        share of exactly 0.0: the row ignores the column (the slot is dead, as
+        an inactive column's under set_active).  share: a C x C array, C <=
+        LQRO_CLASSES_MAX, copied.  cls: a numpy integer array of n_agents
+        entries below C (copied; another length, an entry outside 0..C-1 or a
+        share outside [0, 1] raises ValueError).  device=True: cls is a uint8
+        torch tensor of n_agents bytes on the context's device, or an integer
+        device pointer to as many, read when each step runs (rewrite it on the
+        step's stream before the step; the tensor is kept alive here; a byte
+        >= C reads as C - 1).  cls or share None clears: no table."""
+        n = self.cfg.n_agents
+        if cls is None or share is None:
+            _check(lib().lqro_set_interaction(self._h, None, 0, None), "lqro_set_interaction")
+            self._ix_keep = None
+            return
+        sh = np.ascontiguousarray(share, dtype=np.float64)
+        if sh.ndim != 2 or sh.shape[0] != sh.shape[1] or not 1 <= sh.shape[0] <= LQRO_CLASSES_MAX:
+            raise ValueError(f"set_interaction: share is C x C, 1 <= C <= {LQRO_CLASSES_MAX}")
+        if not (np.isfinite(sh).all() and (sh >= 0.0).all() and (sh <= 1.0).all()):
+            raise ValueError("set_interaction: every share lies in [0, 1]")
+        nc = int(sh.shape[0])
+        if device:
+            if isinstance(cls, (int, np.integer)) and not isinstance(cls, (bool, np.bool_)):
+                ptr, keep = int(cls), None
+            elif hasattr(cls, "data_ptr"):
+                import torch
+                if cls.dtype != torch.uint8 or not cls.is_cuda or not cls.is_contiguous() or cls.numel() != n:
+                    raise ValueError(f"set_interaction: need a contiguous uint8 device tensor of {n} bytes")
+                ptr, keep = cls.data_ptr(), cls
+            else:
+                raise ValueError("set_interaction: device=True takes a device tensor or pointer")
+            _check(lib().lqro_set_interaction_device(self._h, C.c_void_p(ptr), nc, _p(sh)),
+                   "lqro_set_interaction_device")
+            self._ix_keep = keep
+            return
+        k = np.asarray(cls)
+        if k.dtype.kind not in "iu":
+            raise ValueError("set_interaction: cls is an integer array")
+        if k.ndim != 1 or k.shape[0] != n:
+            raise ValueError(f"set_interaction: {k.shape} entries for {n} agents")
+        if n and (k.min() < 0 or k.max() >= nc):
+            raise ValueError(f"set_interaction: a class outside 0..{nc - 1}")
+        k = np.ascontiguousarray(k, dtype=np.uint8)
+        _check(lib().lqro_set_interaction(self._h, _p(k), nc, _p(sh)), "lqro_set_interaction")
+        self._ix_keep = None
 
     def set_hard_planes(self, level: int):
         """Which planes linearProgram4 keeps out of its relaxation
@@ -1194,6 +1249,11 @@ class Simulator:
         newV at zero; update() goes on propagating every agent."""
         self.ctx.set_active(mask)
 
+    def set_interaction(self, cls, share, device=False):
+        """Who of qlist avoids whom, and by how much (Context.set_interaction;
+        None: no table).  It governs step() alone."""
+        self.ctx.set_interaction(cls, share, device=device)
+
     def clearance(self):
         """Context.clearance on the agents' current estimates q.x."""
         return self.ctx.clearance(np.stack([q.x for q in self.qlist]))
@@ -1450,6 +1510,11 @@ class DeviceLoop:
         global array; Context.set_active).  It governs step() alone: update()
         goes on propagating every own agent."""
         self.ctx.set_active(mask)
+
+    def set_interaction(self, cls, share, device=False):
+        """This rank's context takes the interaction classes (every rank the
+        same global class array and table; Context.set_interaction)."""
+        self.ctx.set_interaction(cls, share, device=device)
 
     def monitor(self, reset: bool = False):
         """This rank's (last, since_reset) clearance totals (Context.monitor);
