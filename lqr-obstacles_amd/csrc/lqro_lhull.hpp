@@ -428,6 +428,41 @@ __device__ __forceinline__ void lh_scan_batch(LHullL& L, const P* C, int nc, int
   hl_bar();
 }
 
+// does live point q (rounded) coincide with a vertex of face f, bit for bit?
+__device__ __forceinline__ bool lh_on_vertex(const LHullL& L, int f, const double* Pr, int q) {
+  bool on = false;
+  for (int e = 0; e < 3; ++e) {
+    const double* v = L.vx[L.fv[f][e]];
+    on |= Pr[3 * q] == v[0] && Pr[3 * q + 1] == v[1] && Pr[3 * q + 2] == v[2];
+  }
+  return on;
+}
+
+// lh_scan_batch for one face, the points that coincide with its vertices left
+// out as its vertices are: a second copy of a vertex (two of the pair's points
+// can round to the same coordinates) lies in the face's plane and is no sign
+// of near-coplanar input.  The hull's vertex is the copy with the lowest id
+// in every hull kernel and in the oracle (furthest points and support points
+// take the lowest id on ties), so the facet stays the full hull's.  Off the
+// hot path: run only where the batch scan's arg-max is such a copy.
+// Workgroup-wide; the result in every thread.
+template <class P>
+__device__ __forceinline__ void lh_scan_nodup(LHullL& L, const P* C, int nc, int f, const double* Pr,
+                                              double& key, int& idx) {
+  const double n0 = L.fn[f][0], n1 = L.fn[f][1], n2 = L.fn[f][2];
+  const double* a = L.vx[L.fv[f][0]];
+  const double a0 = a[0], a1 = a[1], a2 = a[2];
+  key = -INFINITY; idx = INT_MAX;
+  for (int k = threadIdx.x; k < nc; k += blockDim.x) {
+    const double4 c = C[k];
+    const int q = (int)c.w;
+    if (lh_on_vertex(L, f, Pr, q)) continue;   // (the face's own vertices among them)
+    const double d = n0 * (c.x - a0) + n1 * (c.y - a1) + n2 * (c.z - a2);
+    if (d > key || (d == key && q < idx)) { key = d; idx = q; }
+  }
+  hl_argmax(L, key, idx);
+}
+
 // hull_points for k_lhull: the same points, in the same order and
 // arithmetic, with the row's T_k, the sphere and the pair's translations
 // staged in LDS (the lp region, free until the first compaction), one
@@ -576,9 +611,17 @@ __device__ __forceinline__ void lhull_body(const HullArgs& A, LHullL& L) {
           // gone, or its slot now holds a face of an earlier insertion
           if (!L.alive[f] || L.fv[f][0] != L.bt[b][0] || L.fv[f][1] != L.bt[b][1] || L.fv[f][2] != L.bt[b][2])
             continue;
-          const double key = L.bkey[b], nn = L.fn[f][3];
+          double key = L.bkey[b];
+          int kidx = L.bidx[b];
+          const double nn = L.fn[f][3];
+          // nothing beyond f, and the nearest point is a copy of one of its
+          // vertices: look past the copies (uniform: every thread reads LDS)
+          if (!(key > 0.0 && key * key > eps2 * nn) && kidx != INT_MAX && lh_on_vertex(L, f, Pr, kidx)) {
+            if (L.inlds) lh_scan_nodup(L, L.lp, L.nc, f, Pr, key, kidx);
+            else lh_scan_nodup(L, L.cb ? C1 : C0, L.nc, f, Pr, key, kidx);
+          }
           if (key > 0.0 && key * key > eps2 * nn) {
-            lh_insert(L, Pr, L.bidx[b], eps2, band2, J.vrel);
+            lh_insert(L, Pr, kidx, eps2, band2, J.vrel);
           } else if (key > 0.0 || key * key <= band2 * nn) {
             if (tid == 0) L.fail = 22;                   // a point near the facet's plane
             hl_bar();

@@ -956,6 +956,44 @@ class Context:
             return r, int(nf.value), fl[: end[0] if len(end) else max_facets]
         return r, int(nf.value)
 
+    def debug_hull(self, points: np.ndarray, vrel, mode: int = 0, max_facets: int = 0):
+        """Test hook (lqro_debug_hull_points_ex): the canonical rule's hull
+        kernels on given points (already %g-rounded; n <= H * NP): mode 0
+        k_hull, 1 k_lhull, 3 k_hull_big alone, 4 k_hull then k_hull_big on its
+        retry queue, as the step launches them.  Returns (record, facets,
+        status).  facets: k_hull's facet list (point ids, k x 3) where it
+        finished a build (modes 0 and 4), else None.  status, modes 0 and 4:
+        k_hull's facet count, -2: it handed the points to k_hull_big (mode 4:
+        which has decided; the record is its); mode 3: the record's facet
+        count, -1: no hull; mode 1: 0 when k_lhull decided, else its hand-over
+        reason (its fail code 21..35; 20: the point set or the initial
+        tetrahedron).  self.debug_hull_fails (modes 0, 3, 4): the fail codes
+        the call's builds ended with, ascending (1 the vertex cap, 4 the face
+        slots, 8 a degenerate set, ...; empty: every build finished)."""
+        if mode not in (0, 1, 3, 4):
+            raise ValueError("debug_hull: mode 0, 1, 3 or 4 (k_qhull: debug_qhull)")
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        v = np.ascontiguousarray(vrel, dtype=np.float64)
+        lists = mode in (0, 4)
+        cap = (max_facets if max_facets > 0 else 2 * pts.shape[0]) if lists else 1   # (a hull has 2n - 4 facets at most)
+        fl = np.zeros((cap, 3), np.int32)
+        rec = PairRecord()
+        nf = C.c_int32()
+        reason = np.zeros(16, np.int64)
+        fn = lib().lqro_debug_hull_points_ex
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                       C.POINTER(C.c_int32), C.POINTER(PairRecord), C.c_void_p]
+        _check(fn(self._h, _p(pts), pts.shape[0], _p(v), mode, _p(fl) if lists else None, cap if lists else 0,
+                  C.byref(nf), C.byref(rec), _p(reason)), "lqro_debug_hull_points_ex")
+        r = np.frombuffer(bytes(rec), dtype=RECORD_DTYPE)[0]
+        status = int(nf.value)
+        self.debug_hull_fails = () if mode == 1 else tuple(int(k) for k in np.nonzero(reason[1:])[0] + 1)
+        if mode == 1:
+            k = np.nonzero(reason)[0]
+            status = 0 if status == 0 else 20 + int(k[0]) if len(k) else -1
+        facets = fl[:min(status, cap)].copy() if lists and status > 0 else None
+        return r, facets, status
+
     def timings(self) -> dict:
         t = np.zeros(4, dtype=np.float32)
         _check(lib().lqro_get_timings(self._h, _p(t)), "lqro_get_timings")

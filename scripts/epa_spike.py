@@ -46,11 +46,13 @@ def rule_value(R, P, v, t):
     return abs(n[0] * (v[0] - p0[0]) + n[1] * (v[1] - p0[1]) + n[2] * (v[2] - p0[2])), n
 
 
-def local(R, P, v, ring=True):
+def local(R, P, v, ring=True, vmax=None):
     """Returns (value, canonical triple, |V|, support queries), or None when
     vrel is not strictly inside the local hull (the full hull decides then).
     ring: also certify every facet sharing a vertex with a window facet — with
-    vrel inside Q that makes the window complete."""
+    vrel inside Q that makes the window complete.
+    vmax: give up once Q has more than vmax vertices: (None, None, |V|,
+    queries), undecided."""
     scale = np.abs(R).max()
     eps = 1e-13 * (scale + 1.0)
     delta = np.sqrt(((P - R) ** 2).sum(1)).max() * (1 + 1e-9) + 1e-12
@@ -58,6 +60,8 @@ def local(R, P, v, ring=True):
     queries = 0
     cert = {}                      # triple (as produced) -> rule value; P-facets
     while True:
+        if vmax is not None and len(V) > vmax:
+            return None, None, len(V), queries
         F = [tuple(V[k] for k in f) for f in pyoracle.hull(R[V])]
         info = {}
         for t in F:
